@@ -10,7 +10,7 @@ states: BLOSUM62 with affine gaps, BLAST's default 11/1 (a gap of k residues
 costs 11 + k, i.e. gap_open 12 and gap_extend 1 in this library's
 convention).  The reference's own scoring (BLOSUM50 of SWSolver.cu:54-81,
 linear gap 2) is timed the same way right after and reported under
-"reference_scoring".
+"reference_scoring" (--full).
 
 --config c3: the 20 shipped queries (144..5478 aa, sum 41,752) as one batch
 against the same database (configs[2]); --config c4: P07327 against a
@@ -33,12 +33,26 @@ Multi-GPU (torchrun, one process per GPU) is STRONG scaling: every rank
 builds the same database and scans only its residue-balanced share (LPT over
 subject lengths, dist.shard_indices; C4: an id range), so N GPUs search one
 database of fixed size.  value = all cells of the database / the max-over-
-ranks time of K steps.  After timing, every rank re-scores its share with
+ranks time of K steps.  After timing (--full), every rank re-scores its share with
 the CPU oracle (all of it when that fits --verify-seconds, else a random
 sample plus its top-K hits), checks its device top-K against a CPU top-K of
 its scores, and rank 0 checks the RCCL-merged top-K against the merge of
 the oracle's per-rank top-K (the bit-exact top-score list of north_star);
 --shard-of N --shard-rank R measures rank R's share of N GPUs on one GPU.
+
+A plain run (no --full) does only what the headline figure needs: set-up,
+the warm-up steps, the --steps timed steps, the result line.  --full adds
+every other leg after the timed steps: the sustained loop, the cold / warm
+single steps, the same steps under the reference's scoring, the oracle
+parity legs and the CPU baseline (c1: the literal cpu.cpp and the GPU on the
+same database).  --dump-outputs DIR (either mode) writes what the last timed
+step computed as DIR/<name>.npy: `scores` (float32 [queries, subjects] of
+this rank's share; a fixed, seeded sample of the subjects, listed in
+`scores_subjects`, when the whole would not fit) and the merged top-K as
+`topk_ids` / `topk_scores` (float64 [queries, K]); 60 MB at the most, over
+every rank's files.  The database, the
+queries and the sample are functions of the arguments alone, so two builds
+run with the same arguments can be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -408,12 +422,61 @@ def _pad_keys(keys, K):
     return out
 
 
+DUMP_BYTES = 60_000_000  # all a dump may take, under the 64 MB allowed: every file of every rank, headers included
+DUMP_HEADER_BYTES = 1024  # four .npy headers per rank (128 B each with these shapes), rounded up
+
+
+def dump_budget(nq, k, world=1):
+    """(bytes one rank's scores and their subject list may take, top-K
+    entries per query that are written): the ranks share DUMP_BYTES equally;
+    the keys (two float64 per entry) take at most half of a share, the best
+    first."""
+    share = DUMP_BYTES // max(world, 1) - DUMP_HEADER_BYTES
+    k = min(k, share // 2 // (16 * max(nq, 1)))
+    return share - 16 * nq * k, k
+
+
+def dump_sample(nq, n, budget):
+    """The subjects (sorted local indices) whose scores a dump holds: all n
+    while nq x n float32 fit `budget` bytes, else as many as fit it together
+    with their float64 index list (4 nq + 8 bytes per subject), drawn from
+    SEED (the same for every run with the same arguments); None = all."""
+    if 4 * nq * n <= budget:
+        return None
+    m = max(budget, 0) // (4 * nq + 8)
+    return np.sort(np.random.default_rng(SEED).choice(n, size=m, replace=False))
+
+
+def dump_outputs(path, scores, final_keys, decode, rank=0, world=1):
+    """--dump-outputs: the last timed step's results as .npy files, at most
+    DUMP_BYTES over all ranks.  scores: int32 [nq, n] of this rank's share
+    (every rank writes its own within its part of the budget; file `scores`
+    at one rank, `scores_rank<r>` otherwise; a sample's subjects beside it as
+    `scores_subjects*`, float64 because float32 does not hold every index);
+    final_keys: int64 [nq, K] merged top-K keys or None (rank 0 writes them,
+    decoded into ids and scores: both exact in float64)."""
+    os.makedirs(path, exist_ok=True)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    nq, n = scores.shape
+    budget, k = dump_budget(nq, 0 if final_keys is None else final_keys.shape[1], world)
+    idx = dump_sample(nq, n, budget)
+    if idx is not None:
+        scores = scores[:, idx]
+        np.save(os.path.join(path, "scores_subjects%s.npy" % suffix), idx.astype(np.float64))
+    np.save(os.path.join(path, "scores%s.npy" % suffix), np.ascontiguousarray(scores, dtype=np.float32))
+    if rank == 0 and final_keys is not None:
+        ids, sc = decode(final_keys[:, :k])
+        np.save(os.path.join(path, "topk_ids.npy"), ids.astype(np.float64))
+        np.save(os.path.join(path, "topk_scores.npy"), sc.astype(np.float64))
+
+
 def c1_main(args):
     """configs[0]: P02232 (144 aa) vs 1,000 synthetic subjects on the CPU
     reference path — the oracle at one thread and at every core this process
     may use, the literal cpu.cpp (oracle/_ref/cpu_ref, +/-3 scoring, prints
     its matrices) on a few pairs beside it, and the GPU on the same database
-    for comparison.  value = the oracle at all cores (the reference path)."""
+    for comparison (those two under --full only).  value = the oracle at all
+    cores (the reference path), best of --steps passes (default 5)."""
     import _swpkg
     sw = _swpkg.load()
     eff, aff, quota = host_cores()
@@ -432,9 +495,12 @@ def c1_main(args):
             best = min(best, time.perf_counter() - t)
         return out, cells / best / 1e9, best
 
+    steps = args.steps or 5
     want, r1, t1 = rate(1, 3)
-    _, rall, tall = rate(threads, 5)
-    out = {"metric": METRIC, "value": round(rall, 3), "unit": "GCUPS", "n_gpus": 0, "steps": 5, "warmup": 0,
+    last, rall, tall = rate(threads, steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, np.asarray(last)[None], None, None)
+    out = {"metric": METRIC, "value": round(rall, 3), "unit": "GCUPS", "n_gpus": 0, "steps": steps, "warmup": 0,
            "ms_per_step": round(tall * 1e3, 3), "higher_is_better": True, "scaling": "none",
            "vs_baseline": None, "dtype": "int32", "data": "synthetic",
            "config": {"workload": "C1: P02232 (144 aa) vs %d synthetic subjects (%d residues), BLOSUM50 "
@@ -442,11 +508,11 @@ def c1_main(args):
                       "config": "c1", "cells": cells},
            "cpu_baseline": {"value": round(rall, 3), "unit": "GCUPS", "cores": threads, "kind": "port",
                             "one_thread": round(r1, 4),
-                            "sample": "the whole C1 database, best of 5 runs at %d threads, best of 3 at one "
-                                      "thread" % threads},
+                            "sample": "the whole C1 database, best of %d runs at %d threads, best of 3 at one "
+                                      "thread" % (steps, threads)},
            "host": {"cores_used": threads, "affinity_cpus": aff, "cgroup_quota_cpus": quota}}
     ref = os.path.join(REPO, "oracle", "_ref", "cpu_ref")
-    if os.path.exists(ref):
+    if args.full and os.path.exists(ref):
         # the literal cpu.cpp: one pair per process, +/-3 scoring, prints
         # its alignment and both matrices (to /dev/null here)
         letters = "ARNDCQEGHILKMFPSTWYVBJZX*"
@@ -464,7 +530,7 @@ def c1_main(args):
                                     "sample": "oracle/_ref/cpu_ref (built from the untouched cpu.cpp) on the first "
                                               "%d pairs, +/-3 scoring as cpu.cpp hard-codes, one process per pair "
                                               "printing its matrices to /dev/null: %.3g cells in %.2f s" % (npairs, c, dt)}
-    if not args.no_gpu:
+    if args.full and not args.no_gpu:
         h = sw.Handle(0)
         db = sw.Database(h, res, offs)
         got = db.scan(q, *scoring)
@@ -620,7 +686,20 @@ def main():
     ap.add_argument("--sustained-seconds", type=float, default=5.0,
                     help="after the timed steps, run the step back to back this long and report it as "
                          "`sustained` (outside value; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: the sustained loop, the cold / warm "
+                         "single steps, the reference's scoring, the oracle parity legs, the CPU baseline "
+                         "(c1: the literal cpu.cpp and the GPU comparison); without it only the headline is "
+                         "measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's scores and merged top-K to DIR as .npy files")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, print the line
+        args.no_reference_scoring = args.no_verify = args.no_cpu_baseline = True
+        args.sustained_seconds = 0.0
+        log("plain run: the timed steps only; the sustained loop (--sustained-seconds), the cold / warm steps, "
+            "the reference's scoring, the parity legs and the CPU baseline run with --full")
     if args.config == "c1":
         return c1_main(args)
     if args.gpus < 1:
@@ -818,6 +897,10 @@ def main():
     cold_first = one_step_ms()
     elapsed_max, cells_all, kt, (kernel, intra_kernel) = timed_loop()
     st = db.stats()  # the coop split of the timed scans
+    if args.dump_outputs:
+        # what the last timed step computed: its score buffer and merged keys
+        dump_outputs(args.dump_outputs, scores_buf[(counter[0] - 1) % NBUF].cpu().numpy()[:, :n],
+                     (final if world > 1 else top).cpu().numpy(), sw.capi.decode_keys, rank, world)
     sustained = None
     if args.sustained_seconds > 0:
         # back to back for >= the stated seconds (every rank runs the same
@@ -827,18 +910,23 @@ def main():
         sustained = sustained_summary(s_elapsed, n_sus, s_cells, s_kt["wave_ms"], s_kt["scans"], world)
     final_keys = (final if world > 1 else top).cpu().numpy()
     top_ids, top_scores = sw.capi.decode_keys(final_keys[0])
-    # the measured run's scores and keys (its last step's buffer), for the parity leg
-    gs = scores_buf[(counter[0] - 1) % NBUF].cpu().numpy()[:, :n]
+    # the measured run's scores and keys (its last step's buffer), for the
+    # parity legs; the scores leave the device only when a leg reads them
+    gs = None
+    if not (args.no_verify and args.no_cpu_baseline):
+        gs = scores_buf[(counter[0] - 1) % NBUF].cpu().numpy()[:, :n]
     dev_top = top.cpu().numpy()
-    # a cold scan next to a warm one: the adaptive routing (which kernel
-    # forms a scan runs depends on what earlier scans of this database
-    # observed: the int16 span of the widest blocks, the intra order) forgotten
-    # by sw_db_reset_adaptive, then the same step again
-    db.reset_adaptive()
-    cold_warm = {"first_scan_ms": cold_first, "after_reset_adaptive_ms": one_step_ms(), "warm_ms": one_step_ms(),
-                 "timed_ms_per_step": round(elapsed_max * 1e3 / args.steps, 4),
-                 "note": "single steps synchronised on both sides (host clock, launch latency included): the "
-                         "database's first step, one after sw_db_reset_adaptive, one after that"}
+    cold_warm = None
+    if args.full:
+        # a cold scan next to a warm one: the adaptive routing (which kernel
+        # forms a scan runs depends on what earlier scans of this database
+        # observed: the int16 span of the widest blocks, the intra order) forgotten
+        # by sw_db_reset_adaptive, then the same step again
+        db.reset_adaptive()
+        cold_warm = {"first_scan_ms": cold_first, "after_reset_adaptive_ms": one_step_ms(), "warm_ms": one_step_ms(),
+                     "timed_ms_per_step": round(elapsed_max * 1e3 / args.steps, 4),
+                     "note": "single steps synchronised on both sides (host clock, launch latency included): the "
+                             "database's first step, one after sw_db_reset_adaptive, one after that"}
 
     ref = None
     r_parity = None
@@ -1010,7 +1098,6 @@ def main():
                                            affine, (valu_hw or {}).get("clock_ghz_under_load")),
             "valu_hw": valu_hw,
             "cold_first_scan_ms": cold_first,
-            "cold_warm": cold_warm,
             "kernels": {"inter": kernel, "intra": intra_kernel},
             # each step's device top-K: one launch per query (sw_topk.hip
             # sw_topk_fused) on the exchange stream, beside the next scan
@@ -1025,6 +1112,8 @@ def main():
                 out["exchange_rehearsed"] = ("each step: device top-%d, a one-rank RCCL all-gather, %d rows "
                                              "copied in, the device merge of %d x %d keys, on the exchange "
                                              "stream beside the next scan" % (K, shard_world - 1, shard_world, K))
+        if cold_warm is not None:
+            out["cold_warm"] = cold_warm
         if ref is not None:
             out["reference_scoring"] = ref
         if sustained is not None:

@@ -8,7 +8,7 @@ import sys
 
 import numpy as np
 
-from conftest import REPO
+from conftest import REPO, read_query
 
 CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
             "vs_baseline", "dtype", "data", "config")
@@ -62,10 +62,22 @@ def test_bench_launches_its_own_ranks(monkeypatch):
     assert cmd[-4:] == ["--gpus", "2", "--backend", "gloo"]
 
 
-def test_bench_c1_json_line():
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--config", "c1", "--no-gpu"],
+def test_bench_c1_json_line(tmp_path, sw, oracle):
+    """--full: every leg of the configuration (cpu.cpp's own build beside the
+    oracle when present); --dump-outputs: the last timed pass's scores."""
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--config", "c1", "--no-gpu", "--full",
+                          "--dump-outputs", str(tmp_path / "out")],
                          capture_output=True, text=True, timeout=300, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
+    dumped = np.load(str(tmp_path / "out" / "scores.npy"))
+    res, offs = sw.synth.database(1000, shard=0)
+    want = oracle.scan(sw.encode(read_query("P02232")), res, offs, mat=sw.capi.builtin_matrix(0), gap_open=2,
+                       gap_extend=2, nthreads=4)
+    assert dumped.dtype == np.float32 and dumped.shape == (1, 1000) and np.array_equal(dumped[0], want)
+    # a few of them against the pure-Python recurrence (not the library the bench itself scored with)
+    q, mat = sw.encode(read_query("P02232")), sw.capi.builtin_matrix(0)
+    for j in (0, 1, 499, 998, 999):
+        assert dumped[0, j] == oracle.score_linear_py(q, res[offs[j]:offs[j + 1]], mat, 2)
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, "bench prints ONE JSON line"
     d = json.loads(lines[0])
@@ -79,6 +91,73 @@ def test_bench_c1_json_line():
         assert k in cb, k
     assert cb["kind"] in ("port", "reference") and cb["cores"] >= 1
     assert 0 < cb["one_thread"] <= cb["value"] * 1.2
+
+
+def test_bench_dump_outputs(tmp_path, sw, monkeypatch):
+    """--dump-outputs: scores as float32 (all subjects while they fit the
+    budget, else the same seeded sample every time, listed beside them) and
+    the merged top-K decoded into float64 ids and scores."""
+    sys.path.insert(0, REPO)
+    import bench
+    rng = np.random.default_rng(7)
+    scores = rng.integers(0, 4000, size=(3, 1000)).astype(np.int32)
+    gids = np.arange(1000, dtype=np.int32)
+    keys = np.stack([bench._pad_keys(sw.dist.local_topk(scores[k], gids, 10), 10) for k in range(3)])
+    bench.dump_outputs(str(tmp_path / "a"), scores, keys, sw.capi.decode_keys)
+    got = np.load(str(tmp_path / "a" / "scores.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, scores)
+    assert not (tmp_path / "a" / "scores_subjects.npy").exists()
+    ids = np.load(str(tmp_path / "a" / "topk_ids.npy"))
+    sc = np.load(str(tmp_path / "a" / "topk_scores.npy"))
+    assert ids.dtype == sc.dtype == np.float64 and ids.shape == sc.shape == (3, 10)
+    for k in range(3):
+        assert np.array_equal(sc[k], np.sort(scores[k])[::-1][:10])
+        assert np.array_equal(scores[k][ids[k].astype(np.int64)], sc[k])
+    # past the budget: a sample of the subjects, the same on every call
+    # (headers, then 3 x 10 keys of 16 B, then 100 subjects of 3 x 4 + 8 B)
+    monkeypatch.setattr(bench, "DUMP_BYTES", bench.DUMP_HEADER_BYTES + 16 * 3 * 10 + 100 * (3 * 4 + 8))
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), scores, keys, sw.capi.decode_keys)
+    idx = np.load(str(tmp_path / "b" / "scores_subjects.npy"))
+    assert idx.shape == (100,) and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < 1000
+    assert np.array_equal(idx, np.load(str(tmp_path / "c" / "scores_subjects.npy")))
+    assert np.array_equal(np.load(str(tmp_path / "b" / "scores.npy")), scores[:, idx.astype(np.int64)])
+    assert np.load(str(tmp_path / "b" / "topk_ids.npy")).shape == (3, 10)
+    # everything written, headers included, stays within the budget
+    assert sum(os.path.getsize(str(p)) for p in (tmp_path / "b").iterdir()) <= bench.DUMP_BYTES
+    # two ranks: each half the budget, rank 1 without the keys
+    for r in (0, 1):
+        bench.dump_outputs(str(tmp_path / "w2"), scores, keys, sw.capi.decode_keys, rank=r, world=2)
+    assert sorted(p.name for p in (tmp_path / "w2").iterdir()) == [
+        "scores_rank0.npy", "scores_rank1.npy", "scores_subjects_rank0.npy", "scores_subjects_rank1.npy",
+        "topk_ids.npy", "topk_scores.npy"]
+    assert sum(os.path.getsize(str(p)) for p in (tmp_path / "w2").iterdir()) <= bench.DUMP_BYTES
+
+
+def test_bench_dump_budget():
+    """A dump takes at most 64 MB in all at every configuration's shape:
+    float32 scores, the float64 subject list of a sample, the float64 top-K
+    ids and scores and the files' headers, over every rank."""
+    sys.path.insert(0, REPO)
+    import bench
+    assert bench.DUMP_BYTES <= 64_000_000
+    # (queries, subjects of the database, ranks): C2, C3, C5, C4 at 1..8 GPUs
+    for nq, total, world in ((1, 570000, 1), (20, 570000, 1), (20, 570000, 8), (1, 10000, 1), (1, 50_000_000, 1),
+                             (1, 50_000_000, 2), (1, 50_000_000, 8)):
+        n = -(-total // world)
+        budget, k = bench.dump_budget(nq, 100, world)
+        assert k == 100
+        idx = bench.dump_sample(nq, n, budget)
+        m = n if idx is None else len(idx)
+        assert idx is None or (m > 0 and idx[-1] < n and np.all(np.diff(idx) > 0))
+        per_rank = 4 * nq * m + (0 if idx is None else 8 * m) + 16 * nq * k + bench.DUMP_HEADER_BYTES
+        assert per_rank * world <= bench.DUMP_BYTES, (nq, total, world, per_rank)
+    # C2 and C3 on one GPU are written whole
+    assert bench.dump_sample(1, 570000, bench.dump_budget(1, 100)[0]) is None
+    assert bench.dump_sample(20, 570000, bench.dump_budget(20, 100)[0]) is None
+    # a top-K too large for the budget is cut to its best entries, within half a rank's share
+    budget, k = bench.dump_budget(1, 10_000_000, 1)
+    assert 0 < k < 10_000_000 and 16 * k <= bench.DUMP_BYTES // 2 and budget >= bench.DUMP_BYTES // 2 - 1024
 
 
 def test_bench_sustained_object():
