@@ -332,6 +332,62 @@ static int check_fault(sw_handle* h) {
     return SW_OK;
 }
 
+// What a scan's fp16 pass flagged, read back without waiting: one or two
+// device words copied to a pinned pair in stream order behind the pass, an
+// event after the copy, and what the readback observes.  A later scan takes
+// it once the event has completed (the adaptive routes, adapt_*); a scan
+// repeating the last observation taken does not read it back again.
+struct Readback {
+    struct Obs {  // scoring key, query hash and length, and (inter) the int16 span the scan ran with
+        uint64_t key = 0, qhash = 0;
+        int32_t qlen = 0, nr = 0;
+        bool operator==(const Obs& o) const { return key == o.key && qhash == o.qhash && qlen == o.qlen && nr == o.nr; }
+    };
+    int32_t* host = nullptr;  // pinned [2]
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    bool seen = false;  // `last` holds an observation
+    Obs sent, last;     // of the pending readback; of the last one taken
+};
+
+namespace {
+// Read w0 (and w1, nullable) back on stream s as observation o, unless a
+// readback is pending or o is the last one taken.
+int readback_record(Readback& r, const Readback::Obs& o, const int32_t* w0, const int32_t* w1, hipStream_t s) {
+    if (r.pending || (r.seen && r.last == o)) return SW_OK;
+    if (!r.host) {
+        HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&r.host), 2 * sizeof(int32_t), hipHostMallocDefault));
+        HIPCHECK(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
+    }
+    HIPCHECK(hipMemcpyAsync(r.host, w0, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (w1) HIPCHECK(hipMemcpyAsync(r.host + 1, w1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipEventRecord(r.ev, s));
+    r.pending = true;
+    r.sent = o;
+    return SW_OK;
+}
+
+// True once per completed readback: r.host holds the words, r.last what they observe.
+bool readback_take(Readback& r) {
+    if (!r.pending || hipEventQuery(r.ev) != hipSuccess) return false;
+    r.pending = false;
+    r.seen = true;
+    r.last = r.sent;
+    return true;
+}
+
+// Forget the pending and the last observation.  A readback still in flight
+// lands in the same pinned words later, in stream order before any readback
+// a later scan issues: ignoring it is safe.
+void readback_reset(Readback& r) { r.pending = r.seen = false; }
+
+void readback_free(Readback& r) {
+    if (r.host) (void)hipHostFree(r.host);
+    if (r.ev) (void)hipEventDestroy(r.ev);
+    r = Readback{};
+}
+}  // namespace
+
 struct sw_db {
     sw_handle* h = nullptr;
     int64_t n = 0;
@@ -366,48 +422,27 @@ struct sw_db {
     int32_t* d_rlbnd_h = nullptr;
     int32_t* d_rlbnd_f = nullptr;
     bool rbnd_tried = false;
-    // the intra chain's order (scan_impl): the fp16 pass's flagged count read
-    // back after the scan (pinned, event-gated), and per scoring the shortest
-    // query seen to flag over half of the long subjects
-    int32_t* h_lcount = nullptr;
-    hipEvent_t lcount_ev = nullptr;
-    bool lcount_pending = false;
-    uint64_t lcount_qhash = 0;
-    bool lcount_seen = false;  // the last observation read back (see icount_seen)
-    uint64_t lseen_key = 0, lseen_qhash = 0;
-    int32_t lseen_qlen = 0;
-    uint64_t lcount_key = 0;
-    int32_t lcount_qlen = 0;
+    // the intra chain's order (adapt_intra_i16_first): the fp16 pass's
+    // flagged count (lcount), and per scoring the shortest query seen to flag
+    // over a third of the long subjects
+    Readback lcount;
     std::vector<std::pair<uint64_t, int32_t>> i16_first;
-    // the inter scan's counterpart: the fp16 pass's flagged count and largest
-    // flagged block (pinned pair, event-gated) and per (scoring, query
-    // length) the span of widest blocks the int16 kernel then takes first
-    int32_t* h_icount = nullptr;
-    hipEvent_t icount_ev = nullptr;
-    bool icount_pending = false;
-    uint64_t icount_key = 0;
-    int32_t icount_qlen = 0;
-    int32_t icount_nr = 0;
-    uint64_t icount_qhash = 0;
-    // the last observation read back: a scan repeating it (same query,
-    // scoring and split) does not read it back again
-    bool icount_seen = false;
-    uint64_t seen_key = 0, seen_qhash = 0;
-    int32_t seen_qlen = 0, seen_nr = 0;
+    // the inter scan's counterpart (adapt_inter_i16_span): the fp16 pass's
+    // flagged count and largest flagged block (icount), and per (scoring,
+    // query length) the span of widest blocks the int16 kernel then takes first
+    Readback icount;
     struct SpanObs {
         uint64_t key;
         int32_t qlen;
         int32_t span;
     };
     std::vector<SpanObs> i16_span;
-    int32_t last_i16_span = 0;
     uint64_t* h_trace = nullptr;         // sw_opts trace_file: host-mapped block timeline
     size_t trace_entries = 0;            // ... its entries: per block, then per merged-launch workgroup
     std::vector<uint32_t> h_blk_groups;  // block widths (16-column groups), widest first
     std::vector<int64_t> h_blk_res;      // unpadded residues per block
     int32_t last_ncoop = 0;              // blocks the last scan gave the coop kernel
     int32_t last_npair = 0;              // blocks the last scan ran by wave pairs
-    bool last_lpt = false;               // the last scan was one merged launch (sw_scan_lpt)
     std::vector<int32_t> h_llen;         // long subjects' lengths, longest first
     // sw_scan_lpt work tables (longest first), per scan shape
     struct LptTable {
@@ -423,7 +458,6 @@ struct sw_db {
     };
     std::vector<LptTable> lpt_tables;
     bool last_pair_merged = false;
-    bool last_drain = false;             // the last scan's merged launch drained its own rescue lists
     // device copies of the merged launch's drain arguments (swk::DrainArgs),
     // one per distinct content (profile slot x list parity x score buffer
     // x query shape): uploaded once, then reused with no copy per scan
@@ -466,6 +500,7 @@ swplan::PlanDb plan_view(const sw_db* db) {
     v.nblocks = db->nblocks;
     v.nlong = db->nlong;
     v.long_threshold = db->long_threshold;
+    v.long_max = db->long_max;
     v.blk_groups = db->h_blk_groups.data();
     v.llen = db->h_llen.data();
     v.opts = &db->h->opts;
@@ -480,34 +515,24 @@ swplan::PlanDb plan_view(const sw_db* db) {
 // the same scoring (skey) has flagged over a third of the long subjects at a
 // query no longer than this one, the int16 form runs first, over all of them
 // (the int16 cell costs ~1.4x the fp16 one, so fp16 first + int16 over the
-// flagged fraction p wins while p < ~0.3).  The last observation is read
-// here once its event has completed (scan_impl_body records it).  opt =
+// flagged fraction p wins while p < ~0.3).  The last observation is taken
+// here once its readback has completed (long_pass records it).  opt =
 // sw_opts intra_i16_first: 0 / 1 never / always, else the observations.
 bool adapt_intra_i16_first(sw_db* db, uint64_t skey, int32_t qlen, int32_t opt) {
-    if (db->lcount_pending && hipEventQuery(db->lcount_ev) == hipSuccess) {
-        db->lcount_pending = false;
-        db->lcount_seen = true;
-        db->lseen_key = db->lcount_key;
-        db->lseen_qhash = db->lcount_qhash;
-        db->lseen_qlen = db->lcount_qlen;
-        if (3 * static_cast<int64_t>(*db->h_lcount) > db->nlong) {
-            bool seen = false;
-            for (auto& e : db->i16_first)
-                if (e.first == db->lcount_key) {
-                    e.second = std::min(e.second, db->lcount_qlen);
-                    seen = true;
-                }
-            if (!seen) db->i16_first.emplace_back(db->lcount_key, db->lcount_qlen);
-        }
+    if (readback_take(db->lcount) && 3 * static_cast<int64_t>(db->lcount.host[0]) > db->nlong) {
+        const Readback::Obs& o = db->lcount.last;
+        bool seen = false;
+        for (auto& e : db->i16_first)
+            if (e.first == o.key) {
+                e.second = std::min(e.second, o.qlen);
+                seen = true;
+            }
+        if (!seen) db->i16_first.emplace_back(o.key, o.qlen);
     }
-    bool intra_i16_first = false;
-    if (opt == 0 || opt == 1) {
-        intra_i16_first = opt == 1;
-    } else {
-        for (const auto& e : db->i16_first)
-            if (e.first == skey && e.second <= qlen) intra_i16_first = true;
-    }
-    return intra_i16_first;
+    if (opt == 0 || opt == 1) return opt == 1;
+    for (const auto& e : db->i16_first)
+        if (e.first == skey && e.second <= qlen) return true;
+    return false;
 }
 
 // The same for the inter scan, per block: long queries under cheap linear
@@ -518,31 +543,24 @@ bool adapt_intra_i16_first(sw_db* db, uint64_t skey, int32_t qlen, int32_t opt) 
 // later queries at least as long run those blocks in int16, by wave pairs
 // beside the fp16 launch.  opt = sw_opts inter_i16_span: n forces n blocks (0: off).
 int32_t adapt_inter_i16_span(sw_db* db, uint64_t skey, int32_t qlen, int32_t opt) {
-    if (db->icount_pending && hipEventQuery(db->icount_ev) == hipSuccess) {
-        db->icount_pending = false;
-        db->icount_seen = true;
-        db->seen_key = db->icount_key;
-        db->seen_qhash = db->icount_qhash;
-        db->seen_qlen = db->icount_qlen;
-        db->seen_nr = db->icount_nr;
-        const int32_t cnt = db->h_icount[0], span = db->h_icount[1] + 1;
+    if (readback_take(db->icount)) {
+        const Readback::Obs& o = db->icount.last;
+        const int32_t cnt = db->icount.host[0], span = db->icount.host[1] + 1;
         // most of [nr, span) flagged: not a few high-scoring hits far out
-        if (cnt > 0 && span > db->icount_nr && 2 * static_cast<int64_t>(cnt) >= span - db->icount_nr) {
+        if (cnt > 0 && span > o.nr && 2 * static_cast<int64_t>(cnt) >= span - o.nr) {
             // keep a staircase per scoring: drop what the new observation
             // dominates (a query at least as long with a span no larger),
             // skip it if an existing one dominates it
-            const uint64_t k = db->icount_key;
-            const int32_t q = db->icount_qlen;
             bool dominated = false;
             for (const auto& e : db->i16_span)
-                if (e.key == k && e.qlen <= q && e.span >= span) dominated = true;
+                if (e.key == o.key && e.qlen <= o.qlen && e.span >= span) dominated = true;
             if (!dominated) {
                 db->i16_span.erase(std::remove_if(db->i16_span.begin(), db->i16_span.end(),
                                                   [&](const sw_db::SpanObs& e) {
-                                                      return e.key == k && e.qlen >= q && e.span <= span;
+                                                      return e.key == o.key && e.qlen >= o.qlen && e.span <= span;
                                                   }),
                                    db->i16_span.end());
-                db->i16_span.push_back({k, q, span});
+                db->i16_span.push_back({o.key, o.qlen, span});
             }
         }
     }
@@ -553,8 +571,7 @@ int32_t adapt_inter_i16_span(sw_db* db, uint64_t skey, int32_t qlen, int32_t opt
         for (const auto& o : db->i16_span)
             if (o.key == skey && o.qlen <= qlen) i16_span = std::max(i16_span, o.span);
     }
-    i16_span = static_cast<int32_t>(std::min<int64_t>(std::max(i16_span, 0), db->nblocks));
-    return i16_span;
+    return static_cast<int32_t>(std::min<int64_t>(std::max(i16_span, 0), db->nblocks));
 }
 
 void free_dev(sw_db* db) {
@@ -582,11 +599,9 @@ void free_dev(sw_db* db) {
     if (db->h_trace) (void)hipHostFree(db->h_trace);  // sized for this block layout
     db->h_trace = nullptr;
     db->trace_entries = 0;
-    db->lcount_pending = false;
-    db->lcount_seen = false;
+    readback_reset(db->lcount);
     db->i16_first.clear();  // the long partition may change
-    db->icount_pending = false;
-    db->icount_seen = false;
+    readback_reset(db->icount);
     db->i16_span.clear();   // ... and the block layout
     db->device_bytes = 0;
     db->built = false;
@@ -1040,41 +1055,36 @@ int build_profiles(sw_handle* h, const uint8_t* q, int32_t qlen, const int8_t* m
     return SW_OK;
 }
 
-// The work table of sw_scan_lpt for this scan shape (built once, cached).
-int lpt_table(sw_db* db, int32_t qpad, int rows, int32_t qpad_intra, int ri, int32_t npair, int32_t nquad,
-              int32_t ntail, bool affine, bool tri, const int32_t** order, int* n, int32_t* npipe_out,
-              int32_t* pipe_tail_out) {
+// The work table of sw_scan_lpt for this scan's shape (built once, cached,
+// the oldest of 8 dropped); null after an error.
+const sw_db::LptTable* lpt_table(sw_db* db, const swplan::ScanPlan& p) {
+    const sw_opts& O = db->h->opts;
+    const bool tri = p.ntri != 0;
     for (const auto& t : db->lpt_tables)
-        if (t.qpad == qpad && t.rows == rows && t.qpad_intra == qpad_intra && t.ri == ri && t.npair == npair && t.group == nquad &&
-            t.tail == ntail && t.pipe_opt == db->h->opts.lpt_pipe && t.affine == affine && t.tri == tri &&
-            t.tail_opt == db->h->opts.lpt_pipe_tail) {
-            *order = t.d_order;
-            *n = t.n;
-            *npipe_out = t.npipe;
-            *pipe_tail_out = t.pipe_tail;
-            return SW_OK;
-        }
-    const swplan::LptPlan pl = swplan::lpt_plan(plan_view(db), qpad, rows, qpad_intra, ri, npair, nquad, ntail,
-                                                affine, tri);
-    const std::vector<int32_t>& ord = pl.order;
-    const std::vector<float>& cost = pl.cost;
-    const int64_t npipe = pl.npipe, pipe_tail = pl.pipe_tail;
-    sw_db::LptTable t{qpad, rows, qpad_intra, ri, npair, nquad, ntail, static_cast<int32_t>(ord.size()), affine, tri,
-                      static_cast<int32_t>(npipe), db->h->opts.lpt_pipe, static_cast<int32_t>(pipe_tail),
-                      db->h->opts.lpt_pipe_tail, nullptr, cost};
-    HIPCHECK(hipMalloc(reinterpret_cast<void**>(&t.d_order), ord.size() * sizeof(int32_t)));
-    HIPCHECK(hipMemcpy(t.d_order, ord.data(), ord.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    db->device_bytes += ord.size() * sizeof(int32_t);
+        if (t.qpad == p.qpad_inter && t.rows == p.lpt_rows && t.qpad_intra == p.qpad_intra2 && t.ri == p.ri2 &&
+            t.npair == p.npair && t.group == p.nquad && t.tail == p.ntail && t.pipe_opt == O.lpt_pipe &&
+            t.affine == p.affine && t.tri == tri && t.tail_opt == O.lpt_pipe_tail)
+            return &t;
+    const swplan::LptPlan pl = swplan::lpt_plan(plan_view(db), p.qpad_inter, p.lpt_rows, p.qpad_intra2, p.ri2, p.npair,
+                                                p.nquad, p.ntail, p.affine, tri);
+    sw_db::LptTable t{p.qpad_inter, p.lpt_rows, p.qpad_intra2, p.ri2, p.npair, p.nquad, p.ntail,
+                      static_cast<int32_t>(pl.order.size()), p.affine, tri, pl.npipe, O.lpt_pipe, pl.pipe_tail,
+                      O.lpt_pipe_tail, nullptr, pl.cost};
+    const size_t bytes = pl.order.size() * sizeof(int32_t);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&t.d_order), bytes);
+    if (e == hipSuccess && (e = hipMemcpy(t.d_order, pl.order.data(), bytes, hipMemcpyHostToDevice)) != hipSuccess)
+        (void)hipFree(t.d_order);
+    if (e != hipSuccess) {
+        fail(SW_E_HIP, std::string("sw_scan_lpt's work table: ") + hipGetErrorString(e));
+        return nullptr;
+    }
+    db->device_bytes += bytes;
     if (db->lpt_tables.size() >= 8) {
         (void)hipFree(db->lpt_tables.front().d_order);
         db->lpt_tables.erase(db->lpt_tables.begin());
     }
-    db->lpt_tables.push_back(t);
-    *order = t.d_order;
-    *n = t.n;
-    *npipe_out = t.npipe;
-    *pipe_tail_out = t.pipe_tail;
-    return SW_OK;
+    db->lpt_tables.push_back(std::move(t));
+    return &db->lpt_tables.back();
 }
 
 // The device copy of a merged launch's drain arguments (swk::DrainArgs: read
@@ -1197,175 +1207,80 @@ int rank_after(sw_handle* h, sw_db* db, const int32_t* scores_dev, const RankReq
     return SW_OK;
 }
 
-// defer: another scan follows on this handle before the caller waits (the
-// queries of a batch but the last): this scan's rescue tail may run on the
-// tail stream beside the next scan's fp16 passes (sw_handle::tail).
-// rq (nullable): rank the scan's scores too (a top-K launch after every
-// stage that writes them, before the scan's end event).
-int scan_impl_body(sw_handle* h, const sw_db* cdb, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
-              int32_t* scores_dev, bool defer = false, const RankReq* rq = nullptr) {
-    sw_db* db = const_cast<sw_db*>(cdb);
-    if (!h || !db || (!query && qlen > 0) || qlen < 0 || !scores_dev) return fail(SW_E_INVALID, "null argument");
-    if (rq) defer = false;  // the ranking reads every rescued score
-    const int8_t* mat;
-    int go, ge, rc;
-    if ((rc = check_fault(h))) return rc;
-    if ((rc = check_scoring(sc, &mat, &go, &ge))) return rc;
-    // The linear kernels keep S + gap in an int8 profile; if that does not
-    // fit, score with the affine kernels (open == extend is the same DP).
-    bool biased_fits = true;
-    for (int k = 0; k < 625; ++k)
-        if (mat[k] + go > 127) biased_fits = false;
-    const bool affine = go != ge || !biased_fits;
-    if (!db->built && (rc = build_db(db))) return rc;
-    HIPCHECK(hipSetDevice(h->device));
-    h->launches = 0;
-    h->had_intra = false;
-    if ((rc = next_events(h))) return rc;
+// ---- one scan: the plan (swplan::scan_plan), then its enqueue stages -------
+// Boundary rows: inter H, F; intra H, F.
+struct BndRows {
+    int32_t *h, *f, *lh, *lf;
+};
+// ... of a scan's passes, and of the rescue tails in stream order behind them
+BndRows pass_rows(const sw_db* db) { return {db->d_bnd_h, db->d_bnd_f, db->d_lbnd_h, db->d_lbnd_f}; }
+// ... of a deferred rescue tail, and of the merged launch's drain (ensure_rbnd)
+BndRows tail_rows(const sw_db* db) { return {db->d_rbnd_h, db->d_rbnd_f, db->d_rlbnd_h, db->d_rlbnd_f}; }
 
-    // The packed int16 kernel is exact when no H, E, F or H_diag + S can
-    // leave int16: H <= qlen * max S, plus one profile entry (+ gap bias).
-    int max_s = 0;
-    for (int k = 0; k < 625; ++k) max_s = std::max<int>(max_s, mat[k]);
-    // Beyond that bound the two-strips kernel runs guarded (saturating lanes
-    // flag their block for int32 re-scoring) as long as one cell's increment
-    // stays far inside the guard band (kSat16 leaves 1152).
-    //   m16 = 2: int16 exact; 1: guarded int16 allowed; 0: int32 only
-    // Affine 16-bit scans run the fp16 biased cell first; its values sit up
-    // to 26 ge above the true ones, so absurd gap / matrix scales (far beyond
-    // any published scheme) go straight to int32.
-    const bool f16_fits = 2 * max_s + 27 * ge + go < 1024;
-    const int x2_ok = !f16_fits                                                   ? 0
-                      : (static_cast<int64_t>(qlen) + 2) * (max_s + go) < 32767 ? 2
-                      : (max_s + go < 1000 && ge < 1000)                       ? 1
-                                                                               : 0;
-    const swk::InterShape shape = swk::inter_shape(affine, x2_ok, h->opts);
-    const int R = shape.R;
-    int32_t qpad_inter = static_cast<int32_t>(round_up(qlen, R));  // (the merged linear launch: see lpt_rows)
-    // (the merged launch's drain takes the int32 rows per lane from ri2, below)
-    int ri = db->nlong ? swk::intra_rows_for(qlen, db->long_max) : 0;
-    int32_t qpad_intra = ri ? static_cast<int32_t>(round_up(qlen, static_cast<int64_t>(swk::kLanes) * ri)) : 0;
-    // Long subjects: two per wave in packed fp16 (sw_intra_x2) when the guard
-    // applies, with the int32 sw_intra re-scoring the subjects it flags
-    // (SW_INTRA_X2=0: int32 only).
-    const sw_opts& O = h->opts;
-    const bool intra_x2 = db->nlong && x2_ok >= 1 && O.intra_x2 != 0;
-    // (20 rows per lane only where no merged launch can take the scan: no
-    // inter blocks; where the fp16 bias of row 19 fits, as f16_fits; and by
-    // the cost model for affine gaps only, see intra_x2_rows_for)
-    const bool ri2_wide = db->nblocks == 0 && 2 * max_s + (swk::intra_bias_rows(swk::kIntraX2MaxRI) + 1) * ge + go < 1024;
-    int ri2 =
-        intra_x2 ? swk::intra_x2_rows_for(qlen, db->long_max, ri2_wide ? (affine ? 2 : 1) : 0, O.intra_x2_rows) : 0;
-    // Affine scans with inter blocks take the merged launch (intra rows 4, 6
-    // or 8 only) even where the cost model prefers more rows per lane for the
-    // long subjects alone: its tail pairs and looped grid win more (C3's long
-    // queries at 8 rows: +1.3 %; under linear gaps the wider form stays,
-    // -6.9 % at 8 rows: profiles/r05_ab/c3_ri8/).  Tentative: a scan that
-    // does not take the merged launch after all (below) gets the cost
-    // model's rows back.
-    const int ri2_model = ri2;
-    if (affine && ri2 > 8 && db->nblocks && O.intra_x2_rows < 0) ri2 = 8;
-    // The intra chain's order from the database's earlier scans
-    // (adapt_intra_i16_first), keyed by the scoring and the query:
-    uint64_t skey = 1469598103934665603ull;  // FNV-1a of the scoring
-    for (int k = 0; k < 625; ++k) skey = (skey ^ static_cast<uint8_t>(mat[k])) * 1099511628211ull;
-    skey = ((skey ^ static_cast<uint32_t>(go)) * 1099511628211ull ^ static_cast<uint32_t>(ge)) * 1099511628211ull;
-    uint64_t qhash = 1469598103934665603ull;  // FNV-1a of the query (which
-    for (int32_t k = 0; k < qlen; ++k) qhash = (qhash ^ query[k]) * 1099511628211ull;  // readbacks repeat)
-    const bool intra_i16_first = adapt_intra_i16_first(db, skey, qlen, O.intra_i16_first) && intra_x2;
-    // ... and the inter scan's widest blocks in int16 first (adapt_inter_i16_span)
-    const int32_t i16_span = adapt_inter_i16_span(db, skey, qlen, O.inter_i16_span);
-    int32_t qpad_intra2 = ri2 ? static_cast<int32_t>(round_up(qlen, static_cast<int64_t>(swk::kLanes) * ri2)) : 0;
-    // Empty query: every score is 0 (the reference's kernel leaves maxScore 0).
-    if (qlen == 0) {
-        db->last_ncoop = 0;
-        db->last_npair = 0;
-        h->last_kernel = "none";
-        h->last_intra = "none";
-        // a non-deferred scan completes on the handle's stream: so do the
-        // earlier scans' deferred tails (a batch may end with an empty query)
-        if (!defer && (rc = join_tails(h))) return rc;
-        MARK(0, h->stream);
-        if (db->max_id >= 0)
-            HIPCHECK(hipMemsetAsync(scores_dev, 0, static_cast<size_t>(db->max_id + 1) * 4, h->stream));
-        if (rq && (rc = rank_after(h, db, scores_dev, *rq))) return rc;
-        for (int k = 1; k < 8; ++k) MARK(k, h->stream);
-        h->timed = true;
-        return SW_OK;
-    }
+// What the stages of one scan share.
+struct Scan {
+    sw_handle* h = nullptr;
+    sw_db* db = nullptr;
+    swplan::ScanPlan plan;
+    swplan::PlanScoring sc;
+    int32_t qlen = 0;
+    uint64_t skey = 0, qhash = 0;  // FNV-1a of the scoring and of the query (what the readbacks observe)
+    int32_t* scores = nullptr;
+    // this scan's list set (scan_lists): inter lists A and B [count, ids...],
+    // the largest flagged block, the drain's dequeue heads of A and B; intra
+    // lists 1 (flagged by the fp16 pass) and 2 (... and again by int16), their
+    // heads; the merged launch's work counter (persistent form)
+    int par = 0;
+    int32_t *listA = nullptr, *listB = nullptr, *maxA = nullptr, *headA = nullptr;
+    int32_t *list1 = nullptr, *list2 = nullptr, *head1 = nullptr;
+    int32_t* lpt_next = nullptr;
+    bool deferred = false;  // the rescue tail runs on its own stream and boundary rows (sw_handle::tail)
     Profiles P;
-    const bool x2 = shape.x2s;
-    // int32 re-scoring of blocks a 16-bit kernel flags near saturation
-    const bool rescue = swk::inter_needs_rescue(shape, x2_ok);
-    const bool f16 = shape.f16;
-    const int32_t qpad_rescue = rescue ? static_cast<int32_t>(round_up(qlen, swk::rescue_rows(affine))) : 0;
-    // fp16 chain stage 2 (the int16 two-strips 32x8 kernel): 64-row passes
-    // (the linear list kernel is the 48x4 shape: 96-row passes)
-    const int32_t qpad_list = f16 ? static_cast<int32_t>(round_up(qlen, affine ? 64 : 96)) : 0;
-    // widest blocks first, one cooperative workgroup each (int32, int8-profile paths)
-    // two-strips scans: the widest blocks by wave pairs (at least two passes)
-    const int32_t npair =
-        (db->nblocks && swk::inter_has_pair(shape) && qpad_inter > R) ? swplan::pair_blocks(plan_view(db)) : 0;
-    const int32_t ncoop =
-        (!npair && db->nblocks) ? swplan::coop_blocks(plan_view(db), swk::inter_coop_divisor(shape)) : 0;
-    db->last_ncoop = ncoop;
-    db->last_npair = npair;
-    db->last_pair_merged = npair != 0;
-    // One merged launch for the fp16 scan, longest work first (sw_scan_lpt):
-    // the inter groups + single waves and the long subjects' fp16 pass, when
-    // the scan takes exactly that shape.  Measured (profiles/r02_strong/lpt/,
-    // r02_round/): C2's 1/8 share 1.92 -> 1.45 ms, 1/4 2.57 -> 2.29.  On the
-    // whole C2 database it was 2 % slower than two concurrent launches until
-    // the launch drained its own rescue lists (no rescue launches or events
-    // after it): now 7.19 -> 7.12 ms under affine scoring (C3 and C4's share
-    // unchanged), but under linear gaps 4.57 -> 5.03 ms (profiles/r04_*/);
-    // since round 5's tail pairs, looped grid and 96-row linear passes the
-    // whole C2 database under linear gaps too: 16,512 -> 16,777 GCUPS
-    // (profiles/r05_ab/lpt_linear_c2/).  Every scan of that shape takes it;
-    // sw_opts lpt 0 / 1 forces either form.
-    const bool lpt_want = O.lpt >= 0 ? O.lpt == 1 : true;
-    const bool lpt = lpt_want && db->nlong && db->nblocks && intra_x2 && !intra_i16_first &&
-                     f16 && rescue && npair && !ncoop && i16_span == 0 &&
-                     swk::lpt_supported(ri2);
-    db->last_lpt = lpt;
-    if (!lpt && ri2 != ri2_model) {  // the separate intra launch: the cost model's shape
-        ri2 = ri2_model;
-        qpad_intra2 = static_cast<int32_t>(round_up(qlen, static_cast<int64_t>(swk::kLanes) * ri2));
-    }
-    // ... and that launch re-scores what it flags itself (sw_scan_lpt's drain,
-    // swk::DrainArgs): no rescue launches after it, on boundary rows of its
-    // own (the deferred tails', when device memory allows them), with the
-    // int32 long-subject stage at the fp16 form's rows per lane
-    const bool drain = lpt && ensure_rbnd(db, affine, intra_x2);
-    db->last_drain = drain;
-    if (drain) {
-        ri = ri2;
-        qpad_intra = static_cast<int32_t>(round_up(qlen, static_cast<int64_t>(swk::kLanes) * ri));
-    }
-    // The merged launch under linear gaps runs 96-row passes (48-row strips):
-    // its widest blocks' wave groups need fewer rounds (a 375-aa query: 4
-    // passes, one round of a quad, against 6 passes and two rounds of 64
-    // rows), and the share's span is those blocks' latency;
-    // the linear cell's registers leave room for the taller strips.  Affine
-    // scans keep 64 rows (their E column would not fit).  sw_opts lpt_rows.
-    const int lpt_rows = (lpt && !affine && O.lpt_rows != 64 && round_up(qlen, 96) > 96) ? 96 : 64;
-    if (lpt_rows == 96) qpad_inter = static_cast<int32_t>(round_up(qlen, 96));
-    const int32_t qpad_coop = ncoop ? static_cast<int32_t>(round_up(qlen, swk::inter_coop_rows())) : 0;
+    // the arguments of the main inter launch, of the int32 long-subject
+    // kernel and of the fp16 / int16 one (scan_args); every other launch of
+    // the scan derives its own from these
+    swk::InterArgs a{};
+    swk::IntraArgs ia{}, x{};
+    bool inter_tail = false, intra_tail = false;  // rescue stages are left to launch after the passes
+};
+
+// Empty query: every score is 0 (the reference's kernel leaves maxScore 0).
+int scan_empty(sw_handle* h, sw_db* db, int32_t* scores_dev, bool defer, const RankReq* rq) {
+    int rc;
+    db->last_ncoop = 0;
+    db->last_npair = 0;
+    h->last_kernel = "none";
+    h->last_intra = "none";
+    // a non-deferred scan completes on the handle's stream: so do the
+    // earlier scans' deferred tails (a batch may end with an empty query)
+    if (!defer && (rc = join_tails(h))) return rc;
+    MARK(0, h->stream);
+    if (db->max_id >= 0) HIPCHECK(hipMemsetAsync(scores_dev, 0, static_cast<size_t>(db->max_id + 1) * 4, h->stream));
+    if (rq && (rc = rank_after(h, db, scores_dev, *rq))) return rc;
+    for (int k = 1; k < 8; ++k) MARK(k, h->stream);
+    h->timed = true;
+    return SW_OK;
+}
+
+// The rescue lists of this scan (allocated on first need, re-initialised
+// after a fault), the boundary rows, and where the rescue tail runs.
+int scan_lists(Scan& c, bool defer) {
+    sw_handle* h = c.h;
+    sw_db* db = c.db;
+    const swplan::ScanPlan& p = c.plan;
+    int rc;
     // lists A and B, the largest flagged block, a spare word, the dequeue
     // heads of A and B (the merged launch's drain); every entry starts at -1
     // (sw_kernels.h: whoever takes an entry resets it)
     const int64_t rstride = 2 * (db->nblocks + 1) + 4;
     const int64_t lstride = 2 * (db->nlong + 1) + 2;  // intra lists 1 and 2, their heads
-    if (rescue && db->nblocks && !db->d_rescue) {
+    if (p.rescue && db->nblocks && !db->d_rescue) {
         HIPCHECK(hipMalloc(reinterpret_cast<void**>(&db->d_rescue), 2 * rstride * sizeof(int32_t)));
         HIPCHECK(hipMemsetAsync(db->d_rescue, 0xff, 2 * rstride * sizeof(int32_t), h->stream));
         db->device_bytes += 2 * rstride * sizeof(int32_t);
     }
-    const bool multi_inter = qpad_inter > R || qpad_rescue > swk::rescue_rows(affine) ||
-                             qpad_coop > swk::inter_coop_rows() || qpad_list > (affine ? 64 : 96);
-    const bool multi_intra = (ri && qpad_intra > swk::kLanes * ri) || (ri2 && qpad_intra2 > swk::kLanes * ri2);
-    if ((multi_inter || multi_intra) && (rc = ensure_bnd(db, affine, intra_x2))) return rc;
-    if (intra_x2 && !db->d_lrescue) {  // two lists: [count, subjects...] x 2
+    if ((p.multi_inter || p.multi_intra) && (rc = ensure_bnd(db, p.affine, p.intra_x2))) return rc;
+    if (p.intra_x2 && !db->d_lrescue) {  // two lists: [count, subjects...] x 2
         HIPCHECK(hipMalloc(reinterpret_cast<void**>(&db->d_lrescue), 2 * lstride * sizeof(int32_t)));
         HIPCHECK(hipMemsetAsync(db->d_lrescue, 0xff, 2 * lstride * sizeof(int32_t), h->stream));
         db->device_bytes += 2 * lstride * sizeof(int32_t);
@@ -1377,471 +1292,541 @@ int scan_impl_body(sw_handle* h, const sw_db* cdb, const uint8_t* query, int32_t
         db->list_epoch = g_fault_epoch.load();
     }
     // this scan's list set; a deferred tail of the scan before last used it
-    const int par = h->parity;
+    c.par = h->parity;
     h->parity ^= 1;
-    if (h->tail_pending[par]) {
-        HIPCHECK(hipStreamWaitEvent(h->stream, h->tail_done[par], 0));
-        h->tail_pending[par] = false;
+    if (h->tail_pending[c.par]) {
+        HIPCHECK(hipStreamWaitEvent(h->stream, h->tail_done[c.par], 0));
+        h->tail_pending[c.par] = false;
     }
     // The drain re-scores on the deferred tails' boundary rows (d_rbnd_*,
     // d_rlbnd_*): a non-merged scan just before this one (a longer query
     // routed int16-first, say) may still be running its tail on those rows,
     // so the merged launch starts after every pending tail.
-    if (drain && (rc = join_tails(h))) return rc;
-    int32_t* const listA = db->d_rescue ? db->d_rescue + par * rstride : nullptr;  // [count, ids...]
-    int32_t* const listB = listA ? listA + db->nblocks + 1 : nullptr;
-    int32_t* const maxA = listA ? listA + 2 * (db->nblocks + 1) : nullptr;
-    int32_t* const list1 = db->d_lrescue ? db->d_lrescue + par * lstride : nullptr;  // flagged by the fp16 pass
-    int32_t* const list2 = list1 ? list1 + db->nlong + 1 : nullptr;                  // ... and again by int16
-    int32_t* const headA = listA ? maxA + 2 : nullptr;  // the drain's dequeue heads: A, B, 1, 2
-    // the merged launch's work counter (the spare word; persistent form)
-    int32_t* const lpt_next = (lpt && listA && O.lpt_persist != 0) ? maxA + 1 : nullptr;
-    int32_t* const head1 = list1 ? list2 + db->nlong + 1 : nullptr;
-    // the rescue tail on its own stream and boundary rows (see sw_handle::tail)
-    const bool deferred = !drain && defer && (!(multi_inter || multi_intra) || ensure_rbnd(db, affine, intra_x2));
-    hipStream_t const ts = deferred ? h->tail : h->stream;
+    if (p.drain && (rc = join_tails(h))) return rc;
+    if (db->d_rescue) {
+        c.listA = db->d_rescue + c.par * rstride;
+        c.listB = c.listA + db->nblocks + 1;
+        c.maxA = c.listA + 2 * (db->nblocks + 1);
+        c.headA = c.maxA + 2;
+        if (p.lpt && h->opts.lpt_persist != 0) c.lpt_next = c.maxA + 1;  // the spare word
+    }
+    if (db->d_lrescue) {
+        c.list1 = db->d_lrescue + c.par * lstride;
+        c.list2 = c.list1 + db->nlong + 1;
+        c.head1 = c.list2 + db->nlong + 1;
+    }
+    c.deferred = !p.drain && defer && (!(p.multi_inter || p.multi_intra) || ensure_rbnd(db, p.affine, p.intra_x2));
+    return SW_OK;
+}
 
-    // the profiles, and the rescue lists' counters (inter A, B, largest
-    // flagged block; intra 1, 2) zeroed by the same launch, before the fork
-    // so the side streams see them
-    {
-        int32_t* const cA = (rescue && db->nblocks) ? listA : nullptr;
-        int32_t* const c1 = (db->nlong && intra_x2) ? list1 : nullptr;
-        int32_t* const reset[10] = {cA, (cA && f16) ? listB : nullptr, (cA && f16) ? maxA : nullptr, c1,
-                                    c1 ? list2 : nullptr, drain ? headA : nullptr, drain ? headA + 1 : nullptr,
-                                    drain ? head1 : nullptr, drain ? head1 + 1 : nullptr, lpt_next};
-        if ((rc = build_profiles(h, query, qlen, mat, go, affine,
-                                 std::max({qpad_inter, qpad_rescue, qpad_coop, qpad_list, qpad_intra2}),
-                                 x2 || intra_x2, ri, qpad_intra, reset, &P)))
-            return rc;
+// The profiles, and the rescue lists' counters (inter A, B, largest flagged
+// block; intra 1, 2; the drain's heads; the work counter) zeroed by the same
+// launch, before the fork so the side streams see them.
+int scan_profiles(Scan& c, const uint8_t* query, const int8_t* mat) {
+    const swplan::ScanPlan& p = c.plan;
+    const bool d = p.drain;
+    int32_t* const cA = (p.rescue && c.db->nblocks) ? c.listA : nullptr;
+    int32_t* const c1 = p.intra_x2 ? c.list1 : nullptr;
+    int32_t* const reset[10] = {cA, (cA && p.f16) ? c.listB : nullptr, (cA && p.f16) ? c.maxA : nullptr, c1,
+                                c1 ? c.list2 : nullptr, d ? c.headA : nullptr, d ? c.headA + 1 : nullptr,
+                                d ? c.head1 : nullptr, d ? c.head1 + 1 : nullptr, c.lpt_next};
+    const int rc = build_profiles(c.h, query, c.qlen, mat, c.sc.go, p.affine,
+                                  std::max({p.qpad_inter, p.qpad_rescue, p.qpad_coop, p.qpad_list, p.qpad_intra2}),
+                                  p.shape.x2s || p.intra_x2, p.ri, p.qpad_intra, reset, &c.P);
+    c.h->evpool[c.h->nscans - 1].merged = p.lpt;
+    return rc;
+}
+
+// c.a: the main inter launch (per-wave; wave groups + single waves; merged).
+int inter_args(Scan& c) {
+    sw_db* db = c.db;
+    const swplan::ScanPlan& p = c.plan;
+    const int go = c.sc.go, ge = c.sc.ge;
+    swk::InterArgs& a = c.a;
+    a.residues = db->d_res;
+    a.blk_off = db->d_blk_off;
+    a.blk_groups = db->d_blk_groups;
+    a.blk_cols = db->d_blk_cols;
+    a.lane_ids = db->d_lane_ids;
+    a.nblocks = static_cast<int32_t>(db->nblocks);
+    a.prof = c.P.dev + (p.shape.x2s ? c.P.off16 : c.P.off8);
+    a.prof_stride = c.P.stride;
+    a.qpad = p.qpad_inter;
+    a.gap_open = go;
+    a.gap_extend = ge;
+    a.bnd_h = db->d_bnd_h;
+    a.bnd_f = db->d_bnd_f;
+    a.scores = c.scores;
+    if (c.h->opts.trace_file[0]) {
+        if (!db->h_trace) {
+            // one entry per block, then one per workgroup of a merged
+            // launch (at most nblocks inter + nlong / 8 intra workgroups)
+            db->trace_entries = static_cast<size_t>(2 * db->nblocks + db->nlong + 8);
+            HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&db->h_trace), 32 * db->trace_entries, hipHostMallocMapped));
+            std::memset(db->h_trace, 0, 32 * db->trace_entries);
+        }
+        HIPCHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&a.trace), db->h_trace, 0));
     }
-    h->evpool[h->nscans - 1].merged = lpt;
-    // fork: the side streams start when the main stream reaches ev[0] (the
-    // merged launch has none: its scan time runs from ev[6])
-    if (!lpt) MARK(0, h->stream);
-    h->last_intra = "none";
-    // the long subjects' stream: a side stream, concurrent with the inter
-    // kernels; with the merged launch, the main stream after it (only the
-    // rescue stages are left to run)
-    hipStream_t is = lpt ? h->stream : h->side;
-    swk::IntraArgs lpt_intra{}, lpt_i32{};  // the merged launch's fp16 pass and its drain's int32 stage
-    // the long subjects' kernels: all of them, or (lpt_done) those after the
-    // fp16 pass the merged launch ran
-    // The long subjects' rescue stages (the int16 form over the fp16 pass's
-    // list, then int32 over what is left), on stream st with boundary rows
-    // bh / bf: right after the passes (stream order), or deferred to the
-    // tail stream with the tail's own boundary rows.
-    swk::IntraArgs tail_x{}, tail_ia{};
-    bool intra_tail = false;
-    auto launch_intra_tail = [&](hipStream_t st, int32_t* bh, int32_t* bf) -> int {
-        if (!intra_i16_first) {
-            // the int16 form re-scores the fp16 pass's list (scores near
-            // 2048: high-scoring pairs, or linear scoring with cheap gaps)
-            // and flags near-32767 ones
-            swk::IntraArgs y = tail_x;
-            y.bnd_h = bh;
-            y.bnd_f = bf;
-            y.list_count = list1;
-            y.subj_list = list1 + 1;
-            y.rescue_count = list2;
-            y.rescue_list = list2 + 1;
-            HIPCHECK(swk::launch_intra_x2_list16(y, ri2, st));
-            ++h->launches;
-        }
-        // int32 re-scoring of what is left (device-side list)
-        swk::IntraArgs ia = tail_ia;
-        ia.bnd_h = bh;
-        ia.bnd_f = bf;
-        HIPCHECK(swk::launch_intra(ia, ri, affine, st));
-        ++h->launches;
-        return SW_OK;
-    };
-    // The inter scan's rescue tail: the int16 packed kernel over the blocks
-    // the fp16 kernel flagged (list A: scores near 2048; it flags its own
-    // near-32767 ones into list B), then int32 over list B (list A for the
-    // int16 scans), on stream st with boundary rows bh / bf.
-    swk::InterArgs tail_a{};
-    bool inter_tail = false;
-    auto launch_inter_tail = [&](hipStream_t st, int32_t* bh, int32_t* bf) -> int {
-        if (f16) {
-            swk::InterArgs r = tail_a;
-            r.bnd_h = bh;
-            r.bnd_f = bf;
-            r.qpad = qpad_list;
-            r.blk_list = listA + 1;
-            r.blk_count = listA;
-            r.rescue_list = listB + 1;
-            r.rescue_count = listB;
-            r.rescue_max = nullptr;
-            HIPCHECK(swk::launch_inter_x2s_list(r, affine, st));
-            ++h->launches;
-        }
-        swk::InterArgs r = tail_a;
-        r.bnd_h = bh;
-        r.bnd_f = bf;
-        r.prof = P.dev + P.off8;
-        r.qpad = qpad_rescue;
-        r.blk_list = (f16 ? listB : listA) + 1;
-        r.blk_count = f16 ? listB : listA;
-        r.rescue_list = nullptr;
-        r.rescue_count = nullptr;
-        HIPCHECK(swk::launch_inter_rescue(r, affine, st));
-        ++h->launches;
-        return SW_OK;
-    };
-    // the long subjects' kernels: all of them, or (lpt_done) those after the
-    // fp16 pass the merged launch ran
-    auto launch_long = [&](bool lpt_done) -> int {
-        if (!lpt_done && is != h->stream) HIPCHECK(hipStreamWaitEvent(is, h->ev[0], 0));
-        swk::IntraArgs ia{};
-        ia.residues = db->d_lres;
-        ia.subj_off = db->d_loff;
-        ia.subj_len = db->d_llen;
-        ia.subj_id = db->d_lid;
-        ia.nsubj = static_cast<int32_t>(db->nlong);
-        ia.prof = P.dev + P.intra_off;
-        ia.qpad = qpad_intra;
-        ia.gap_open = go;
-        ia.gap_extend = ge;
-        ia.bnd_h = db->d_lbnd_h;
-        ia.bnd_f = db->d_lbnd_f;
-        ia.scores = scores_dev;
-        h->last_intra = intra_x2 ? "sw_intra_x2<" + std::to_string(ri2) + (intra_i16_first ? ",int16>" : ">")
-                                 : "sw_intra<" + std::to_string(ri) + (affine ? ",affine>" : ",linear>");
-        h->had_intra = true;
-        if (!intra_x2) {  // int32 over every long subject
-            HIPCHECK(swk::launch_intra(ia, ri, affine, is));
-            ++h->launches;
-            return SW_OK;
-        }
-        swk::IntraArgs x = ia;
-        x.prof = P.dev + P.off16;
-        x.prof_stride = P.stride;
-        x.bias = affine ? 0 : go;  // the linear profile holds S + gap
-        x.qpad = qpad_intra2;
-        // biased cell: stored values up to (RI + 10) ge above the true ones,
-        // offset by zero = -2048 + 2 ge as the inter cell's (the lowest value
-        // an addition reads is a rebased row -1 H of bias -2 ge: exact)
+    if (p.rescue) {
+        a.rescue_count = c.listA;
+        a.rescue_list = c.listA + 1;
+        if (p.f16) a.rescue_max = c.maxA;  // counters reset before the fork
+        // fp16 exact range: every integer in [-2048, 2048].  The cell
+        // stores true + bias + zero with zero = -2048 + 2 ge, which
+        // nearly doubles the range of true values: the lowest value a
+        // later addition reads is a rebased H of bias -ge (>= -2048:
+        // exact); values further below lose to the floor, which sits at
+        // zero or above, and only need their order.  H grows by <= max S
+        // per cell and the biased cell stores values up to 26 ge above
+        // the true ones (bias (15 + 7 + 2) ge, + 2 ge in the profile).
         const int zero = -kF16Span + 2 * ge;
-        x.sat_limit = kF16Span - zero - 2 * std::max(max_s, 1) - swk::intra_bias_rows(ri2) * ge;
-        for (int j = 0; j < swk::kIntraSteps; ++j) x.f16_step[j] = f16_pair(j * ge + zero);
-        x.f16_zero = f16_pair(zero);
-        x.f16_gog = f16_pair(go - ge);
-        if (intra_i16_first) {
-            // the int16 form over every long subject, flagging near-32767 ones
-            x.rescue_count = list2;
-            x.rescue_list = list2 + 1;
-            HIPCHECK(swk::launch_intra_x2_int16(x, ri2, is));
-            h->launches += 1;
-        } else {
-            x.rescue_count = list1;
-            x.rescue_list = list1 + 1;
-            if (lpt && !lpt_done) {  // the merged launch runs this pass
-                lpt_intra = x;
-                lpt_i32 = ia;
-                return SW_OK;
-            }
-            if (!lpt_done) {
-                HIPCHECK(swk::launch_intra_x2(x, ri2, is));
-                ++h->launches;
-            }
-            // the fp16 pass's flagged count, read by a later scan
-            if (!db->h_lcount) {
-                HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&db->h_lcount), sizeof(int32_t),
-                                       hipHostMallocDefault));
-                HIPCHECK(hipEventCreateWithFlags(&db->lcount_ev, hipEventDisableTiming));
-            }
-            const bool lseen = db->lcount_seen && db->lseen_key == skey && db->lseen_qhash == qhash &&
-                               db->lseen_qlen == qlen;
-            if (!db->lcount_pending && !lseen) {
-                HIPCHECK(hipMemcpyAsync(db->h_lcount, list1, sizeof(int32_t), hipMemcpyDeviceToHost, is));
-                HIPCHECK(hipEventRecord(db->lcount_ev, is));
-                db->lcount_pending = true;
-                db->lcount_key = skey;
-                db->lcount_qlen = qlen;
-                db->lcount_qhash = qhash;
-            }
-            if (drain) return SW_OK;  // the merged launch re-scored its flagged subjects itself
-        }
-        tail_x = x;
-        tail_ia = ia;
-        tail_ia.list_count = list2;
-        tail_ia.subj_list = list2 + 1;
-        intra_tail = true;
-        if (deferred) {  // after the fp16 pass; launched on the tail stream below
-            HIPCHECK(hipEventRecord(h->side_done, is));
-            return SW_OK;
-        }
-        return launch_intra_tail(is, db->d_lbnd_h, db->d_lbnd_f);
-    };
-    if (db->nlong && (rc = launch_long(false))) return rc;
-    if (!lpt) MARK(1, db->nlong ? is : h->stream);
-    if (db->nblocks) {
-        swk::InterArgs a{};
-        a.residues = db->d_res;
-        a.blk_off = db->d_blk_off;
-        a.blk_groups = db->d_blk_groups;
-        a.blk_cols = db->d_blk_cols;
-        a.lane_ids = db->d_lane_ids;
-        a.nblocks = static_cast<int32_t>(db->nblocks);
-        a.prof = P.dev + (x2 ? P.off16 : P.off8);
-        a.prof_stride = P.stride;
-        a.qpad = qpad_inter;
-        a.gap_open = go;
-        a.gap_extend = ge;
-        a.bnd_h = db->d_bnd_h;
-        a.bnd_f = db->d_bnd_f;
-        a.scores = scores_dev;
-        if (O.trace_file[0]) {
-            if (!db->h_trace) {
-                // one entry per block, then one per workgroup of a merged
-                // launch (at most nblocks inter + nlong / 8 intra workgroups)
-                db->trace_entries = static_cast<size_t>(2 * db->nblocks + db->nlong + 8);
-                HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&db->h_trace), 32 * db->trace_entries,
-                                       hipHostMallocMapped));
-                std::memset(db->h_trace, 0, 32 * db->trace_entries);
-            }
-            HIPCHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&a.trace), db->h_trace, 0));
-        }
-        // the widest blocks the int16 kernel takes first (see i16_span)
-        const int32_t nr = (f16 && rescue && npair && !ncoop) ? i16_span : 0;
-        db->last_i16_span = nr;
-        if (rescue) {
-            a.rescue_count = listA;
-            a.rescue_list = listA + 1;
-            if (f16) a.rescue_max = maxA;  // counters reset before the fork
-            // fp16 exact range: every integer in [-2048, 2048].  The cell
-            // stores true + bias + zero with zero = -2048 + 2 ge, which
-            // nearly doubles the range of true values: the lowest value a
-            // later addition reads is a rebased H of bias -ge (>= -2048:
-            // exact); values further below lose to the floor, which sits at
-            // zero or above, and only need their order.  H grows by <= max S
-            // per cell and the biased cell stores values up to 26 ge above
-            // the true ones (bias (15 + 7 + 2) ge, + 2 ge in the profile).
-            const int zero = -kF16Span + 2 * ge;
-            a.sat_limit = kF16Span - zero - 2 * std::max(max_s, 1) - 26 * ge;
-            for (int j = 0; j < 32; ++j) a.f16_step[j] = f16_pair(j * ge + zero);
-            a.f16_gog = f16_pair(go - ge);
-            a.f16_zero = f16_pair(zero);
-            a.f16_diff[0] = f16_pair(4 * ge);
-            a.f16_diff[1] = f16_pair(8 * ge);
-            a.f16_diff[2] = f16_pair(16 * ge);
-        }
-        if (ncoop) {
-            // on its own stream, so the per-wave kernel fills the GPU beside it
-            swk::InterArgs c = a;
-            c.qpad = qpad_coop;
-            c.prof = P.dev + P.off8;  // the coop kernel reads the int8 profile
-            HIPCHECK(hipStreamWaitEvent(h->side2, h->ev[0], 0));
-            MARK(4, h->side2);
-            HIPCHECK(swk::launch_inter_coop(c, ncoop, affine, h->opts.coop_skew != 0, h->side2));
-            MARK(5, h->side2);
-            HIPCHECK(hipEventRecord(h->coop_done, h->side2));
-            ++h->launches;
-            a.blk_first = ncoop;
-        } else if (nr) {
-            // blocks [0, nr) in int16 by wave pairs beside the fp16 launch;
-            // their near-32767 ones go to list B (the int32 stage)
-            swk::InterArgs c = a;
-            c.nblocks = nr;
-            c.blk_base = 0;
-            c.rescue_list = listB + 1;
-            c.rescue_count = listB;
-            c.rescue_max = nullptr;
-            HIPCHECK(hipEventRecord(h->fork2, h->stream));
-            HIPCHECK(hipStreamWaitEvent(h->side2, h->fork2, 0));
-            MARK(4, h->side2);
-            HIPCHECK(swk::launch_inter_x2p(c, affine, false, false, 2, h->side2));
-            MARK(5, h->side2);
-            HIPCHECK(hipEventRecord(h->coop_done, h->side2));
-            ++h->launches;
-        }
-        MARK(6, h->stream);
-        int32_t ntail = 0;  // merged launch: the narrowest blocks by pairs
-        int32_t ntri = 0;   // ... and the widest by 3-wave groups
-        if (lpt) {
-            // one launch: the inter groups + single waves and the long
-            // subjects' fp16 pass, longest work first; then the long
-            // subjects' rescue stages
-            a.blk_base = 0;
-            a.blk_first = npair;
-            const int32_t* order = nullptr;
-            int nwg = 0;
-            ntri = affine ? swplan::lpt_tri_blocks(plan_view(db), npair, qpad_inter / lpt_rows) : 0;
-            const int32_t nquad = ntri ? ntri : swplan::lpt_quad_blocks(plan_view(db), npair);
-            a.blk_quad = nquad;
-            a.blk_tri = ntri ? 1 : 0;
-            ntail = swplan::lpt_tail_blocks(plan_view(db), npair, qpad_inter / lpt_rows);
-            a.blk_tail = static_cast<int32_t>(db->nblocks) - ntail;
-            int32_t npipe = 0, pipe_tail = 0;
-            if ((rc = lpt_table(db, qpad_inter, lpt_rows, qpad_intra2, ri2, npair, nquad, ntail, affine, ntri != 0,
-                                &order, &nwg, &npipe, &pipe_tail)))
-                return rc;
-            lpt_intra.pipe_pairs = npipe;
-            lpt_intra.pipe_tail = pipe_tail;
-            const swk::DrainArgs* dargs = nullptr;
-            if (drain) {
-                // the four rescue stages of launch_inter_tail / launch_intra_tail,
-                // on the tails' boundary rows (sw_kernels.h DrainArgs)
-                swk::DrainArgs d{};
-                d.a16 = a;
-                d.a16.bnd_h = db->d_rbnd_h;
-                d.a16.bnd_f = db->d_rbnd_f;
-                d.a16.qpad = qpad_list;
-                d.a16.rescue_list = listB + 1;
-                d.a16.rescue_count = listB;
-                d.a16.rescue_max = nullptr;
-                d.a16.trace = nullptr;
-                d.a32 = a;
-                d.a32.bnd_h = db->d_rbnd_h;
-                d.a32.bnd_f = db->d_rbnd_f;
-                d.a32.prof = P.dev + P.off8;
-                d.a32.qpad = qpad_rescue;
-                d.a32.rescue_list = nullptr;
-                d.a32.rescue_count = nullptr;
-                d.a32.rescue_max = nullptr;
-                d.a32.trace = nullptr;
-                d.i16 = lpt_intra;
-                d.i16.bnd_h = db->d_rlbnd_h;
-                d.i16.bnd_f = db->d_rlbnd_f;
-                d.i16.rescue_list = list2 + 1;
-                d.i16.rescue_count = list2;
-                d.i32 = lpt_i32;
-                d.i32.bnd_h = db->d_rlbnd_h;
-                d.i32.bnd_f = db->d_rlbnd_f;
-                d.lists[0] = listA;
-                d.lists[1] = listB;
-                d.lists[2] = list1;
-                d.lists[3] = list2;
-                d.heads[0] = headA;
-                d.heads[1] = headA + 1;
-                d.heads[2] = head1;
-                d.heads[3] = head1 + 1;
-                d.fault = h->d_fault;
-                d.spin = O.drain_spin >= 0 ? O.drain_spin : (1 << 22);
-                // (every field of d the blob's bytes depend on)
-                const std::vector<uint64_t> key = {
-                    reinterpret_cast<uint64_t>(P.dev), P.off8, P.off16, P.intra_off, static_cast<uint64_t>(par),
-                    reinterpret_cast<uint64_t>(scores_dev), static_cast<uint64_t>(qlen), skey,
-                    static_cast<uint64_t>(npair) | static_cast<uint64_t>(a.blk_tri) << 32,
-                    static_cast<uint64_t>(nquad) | static_cast<uint64_t>(ntail) << 32,
-                    static_cast<uint64_t>(P.stride),
-                    reinterpret_cast<uint64_t>(a.trace),
-                    static_cast<uint64_t>(ri2) | static_cast<uint64_t>(lpt_rows) << 16 |
-                        static_cast<uint64_t>(npipe) << 32,
-                    static_cast<uint64_t>(static_cast<uint32_t>(pipe_tail)),
-                    static_cast<uint64_t>(static_cast<uint32_t>(d.spin))};
-                if ((rc = drain_blob(db, h->stream, key, d, &dargs))) return rc;
-            }
-            HIPCHECK(swk::launch_scan_lpt(a, lpt_intra, order, nwg, affine, ri2, h->cus, h->stream, dargs, lpt_next,
-                                          O.lpt_persist >= 2 ? O.lpt_persist : 0, lpt_rows));
-            // (a draining launch ends the scan: its end event is ev[3])
-            if (!drain) MARK(7, h->stream);
-            if ((rc = launch_long(true))) return rc;
-        } else if (npair) {
-            // one launch: pairs for blocks [nr, npair), one wave per block after
-            a.blk_base = nr;
-            a.blk_first = std::max(npair, nr);
-            HIPCHECK(swk::launch_inter_x2p(a, affine, f16, true, swplan::pair_group(plan_view(db)), h->stream));
-        } else {
-            HIPCHECK(swk::launch_inter(a, affine, shape, h->stream));
-        }
-        h->last_kernel = swk::inter_kernel_name(shape, affine);
-        if (npair) h->last_kernel.replace(0, std::strlen("sw_inter_x2s"), "sw_inter_x2p");  // + wave pairs
-        if (lpt && lpt_rows == 96) h->last_kernel.replace(h->last_kernel.find("<32,"), 4, "<48,");  // 48-row strips
-        if (nr) h->last_kernel += "+int16[0," + std::to_string(nr) + ")";
-        if (ntail) h->last_kernel += "+tail" + std::to_string(ntail);
-        if (ntri) h->last_kernel += "+tri" + std::to_string(ntri);
-        if (lpt) h->last_kernel += drain ? "+lpt+drain" : "+lpt";
-        if (!lpt) MARK(7, h->stream);
+        a.sat_limit = kF16Span - zero - 2 * std::max(c.sc.max_s, 1) - 26 * ge;
+        for (int j = 0; j < 32; ++j) a.f16_step[j] = f16_pair(j * ge + zero);
+        a.f16_gog = f16_pair(go - ge);
+        a.f16_zero = f16_pair(zero);
+        a.f16_diff[0] = f16_pair(4 * ge);
+        a.f16_diff[1] = f16_pair(8 * ge);
+        a.f16_diff[2] = f16_pair(16 * ge);
+    }
+    // its blocks: [blk_base, blk_first) by wave groups (the merged launch:
+    // quads or tris first, the narrowest by tail pairs), one wave per block
+    // from blk_first on; blocks below run beside it (coop, int16 pairs)
+    if (p.lpt) {
+        a.blk_first = p.npair;
+        a.blk_quad = p.nquad;
+        a.blk_tri = p.ntri ? 1 : 0;
+        a.blk_tail = static_cast<int32_t>(db->nblocks) - p.ntail;
+    } else if (p.npair) {
+        a.blk_base = p.nr;
+        a.blk_first = std::max(p.npair, p.nr);
+    } else {
+        a.blk_first = p.ncoop;
+    }
+    return SW_OK;
+}
+
+// c.ia: the int32 kernel over the long subjects.
+void intra_args(Scan& c) {
+    const sw_db* db = c.db;
+    swk::IntraArgs& ia = c.ia;
+    ia.residues = db->d_lres;
+    ia.subj_off = db->d_loff;
+    ia.subj_len = db->d_llen;
+    ia.subj_id = db->d_lid;
+    ia.nsubj = static_cast<int32_t>(db->nlong);
+    ia.prof = c.P.dev + c.P.intra_off;
+    ia.qpad = c.plan.qpad_intra;
+    ia.gap_open = c.sc.go;
+    ia.gap_extend = c.sc.ge;
+    ia.bnd_h = db->d_lbnd_h;
+    ia.bnd_f = db->d_lbnd_f;
+    ia.scores = c.scores;
+}
+
+// c.x: the two-subjects kernel's first pass, fp16 flagging into list 1 (or
+// int16 over every subject, flagging into list 2).
+void intra_x2_args(Scan& c) {
+    const swplan::ScanPlan& p = c.plan;
+    const int go = c.sc.go, ge = c.sc.ge;
+    swk::IntraArgs& x = c.x;
+    x = c.ia;
+    x.prof = c.P.dev + c.P.off16;
+    x.prof_stride = c.P.stride;
+    x.bias = p.affine ? 0 : go;  // the linear profile holds S + gap
+    x.qpad = p.qpad_intra2;
+    // biased cell: stored values up to (RI + 10) ge above the true ones,
+    // offset by zero = -2048 + 2 ge as the inter cell's (the lowest value
+    // an addition reads is a rebased row -1 H of bias -2 ge: exact)
+    const int zero = -kF16Span + 2 * ge;
+    x.sat_limit = kF16Span - zero - 2 * std::max(c.sc.max_s, 1) - swk::intra_bias_rows(p.ri2) * ge;
+    for (int j = 0; j < swk::kIntraSteps; ++j) x.f16_step[j] = f16_pair(j * ge + zero);
+    x.f16_zero = f16_pair(zero);
+    x.f16_gog = f16_pair(go - ge);
+    int32_t* const flagged = p.intra_i16_first ? c.list2 : c.list1;
+    x.rescue_count = flagged;
+    x.rescue_list = flagged + 1;
+}
+
+int scan_args(Scan& c) {
+    if (c.db->nlong) {
+        intra_args(c);
+        if (c.plan.intra_x2) intra_x2_args(c);
+    }
+    return c.db->nblocks ? inter_args(c) : SW_OK;
+}
+
+// The four rescue stages, on boundary rows r:
+//   a16  int16 blocks over list A, flagging near-32767 ones into list B (fp16 scans);
+//   a32  int32 blocks over list B (list A for the int16 scans);
+//   i16  int16 subject pairs over list 1, flagging into list 2;
+//   i32  int32 subjects over list 2.
+// x: the fp16 pass's arguments as launched.  Launched as the scan's rescue
+// tail (launch_inter_tail, launch_intra_tail), or in_launch: run by the
+// merged launch itself (swk::DrainArgs), which takes its entries from
+// DrainArgs::lists instead of the stages' list fields and keeps the block
+// timeline (trace) and the largest flagged block to its fp16 pass.
+struct RescueStages {
+    swk::InterArgs a16, a32;
+    swk::IntraArgs i16, i32;
+};
+RescueStages rescue_stages(const Scan& c, const swk::IntraArgs& x, const BndRows& r, bool in_launch) {
+    const swplan::ScanPlan& p = c.plan;
+    auto items = [](int32_t* list) { return list ? list + 1 : nullptr; };
+    int32_t* const l32 = p.f16 ? c.listB : c.listA;
+    RescueStages s{c.a, c.a, x, c.ia};
+    s.a16.bnd_h = s.a32.bnd_h = r.h;
+    s.a16.bnd_f = s.a32.bnd_f = r.f;
+    s.a16.qpad = p.qpad_list;
+    s.a16.rescue_list = items(c.listB);
+    s.a16.rescue_count = c.listB;
+    s.a16.rescue_max = nullptr;
+    s.a32.prof = c.P.dev + c.P.off8;
+    s.a32.qpad = p.qpad_rescue;
+    s.a32.rescue_list = nullptr;
+    s.a32.rescue_count = nullptr;
+    s.i16.bnd_h = s.i32.bnd_h = r.lh;
+    s.i16.bnd_f = s.i32.bnd_f = r.lf;
+    s.i16.rescue_list = items(c.list2);
+    s.i16.rescue_count = c.list2;
+    if (in_launch) {
+        s.a16.trace = s.a32.trace = nullptr;
+        s.a32.rescue_max = nullptr;
+    } else {
+        s.a16.blk_list = items(c.listA);
+        s.a16.blk_count = c.listA;
+        s.a32.blk_list = items(l32);
+        s.a32.blk_count = l32;
+        s.i16.subj_list = items(c.list1);
+        s.i16.list_count = c.list1;
+        s.i32.subj_list = items(c.list2);
+        s.i32.list_count = c.list2;
+    }
+    return s;
+}
+
+// The inter scan's rescue tail on stream st: the int16 packed kernel over
+// the blocks the fp16 kernel flagged (scores near 2048), then int32 over
+// what that flags (near 32767).
+int launch_inter_tail(Scan& c, hipStream_t st, const RescueStages& s) {
+    if (c.plan.f16) {
+        HIPCHECK(swk::launch_inter_x2s_list(s.a16, c.plan.affine, st));
+        ++c.h->launches;
+    }
+    HIPCHECK(swk::launch_inter_rescue(s.a32, c.plan.affine, st));
+    ++c.h->launches;
+    return SW_OK;
+}
+
+// The long subjects' rescue tail on stream st: the int16 form over the fp16
+// pass's list (high-scoring pairs, or linear scoring with cheap gaps), then
+// int32 over what is left (device-side list).
+int launch_intra_tail(Scan& c, hipStream_t st, const RescueStages& s) {
+    if (!c.plan.intra_i16_first) {
+        HIPCHECK(swk::launch_intra_x2_list16(s.i16, c.plan.ri2, st));
+        ++c.h->launches;
+    }
+    HIPCHECK(swk::launch_intra(s.i32, c.plan.ri, c.plan.affine, st));
+    ++c.h->launches;
+    return SW_OK;
+}
+
+// After the long subjects' first pass on stream is: its rescue stages right
+// behind it, or deferred to the tail stream (deferred_tails).
+int intra_tail(Scan& c, hipStream_t is) {
+    c.intra_tail = true;
+    if (c.deferred) {
+        HIPCHECK(hipEventRecord(c.h->side_done, is));
+        return SW_OK;
+    }
+    return launch_intra_tail(c, is, rescue_stages(c, c.x, pass_rows(c.db), false));
+}
+
+// After every fp16 launch that appends to list A has joined the main
+// stream: the flagged count and largest flagged block, read by a later scan
+// (adapt_inter_i16_span), and the inter rescue stages as intra_tail's.
+int inter_tail(Scan& c) {
+    sw_handle* h = c.h;
+    const swplan::ScanPlan& p = c.plan;
+    int rc;
+    if (p.f16 && p.rescue &&
+        (rc = readback_record(c.db->icount, {c.skey, c.qhash, c.qlen, p.nr}, c.listA, c.maxA, h->stream)))
+        return rc;
+    c.inter_tail = p.rescue && !p.drain;
+    if (!c.inter_tail) return SW_OK;
+    if (c.deferred) {
+        HIPCHECK(hipEventRecord(h->main_done, h->stream));
+        return SW_OK;
+    }
+    return launch_inter_tail(c, h->stream, rescue_stages(c, c.x, pass_rows(c.db), false));
+}
+
+// The long subjects on the side stream, beside the inter kernels.
+int long_pass(Scan& c) {
+    sw_handle* h = c.h;
+    const swplan::ScanPlan& p = c.plan;
+    hipStream_t const is = h->side;
+    int rc;
+    HIPCHECK(hipStreamWaitEvent(is, h->ev[0], 0));
+    h->had_intra = true;
+    ++h->launches;
+    if (!p.intra_x2) {  // int32 over every long subject
+        HIPCHECK(swk::launch_intra(c.ia, p.ri, p.affine, is));
+        return SW_OK;
+    }
+    if (p.intra_i16_first) {
+        // the int16 form over every long subject, flagging near-32767 ones
+        HIPCHECK(swk::launch_intra_x2_int16(c.x, p.ri2, is));
+    } else {
+        HIPCHECK(swk::launch_intra_x2(c.x, p.ri2, is));
+        // the fp16 pass's flagged count, read by a later scan (adapt_intra_i16_first)
+        if ((rc = readback_record(c.db->lcount, {c.skey, c.qhash, c.qlen, 0}, c.list1, nullptr, is))) return rc;
+    }
+    return intra_tail(c, is);
+}
+
+// The inter blocks on the main stream: the widest by the cooperative kernel
+// or (the adaptive span) in int16 by wave pairs on a stream of their own,
+// the rest in one launch.
+int inter_pass(Scan& c) {
+    sw_handle* h = c.h;
+    const swplan::ScanPlan& p = c.plan;
+    if (p.ncoop) {
+        // on its own stream, so the per-wave kernel fills the GPU beside it
+        swk::InterArgs k = c.a;
+        k.blk_first = 0;
+        k.qpad = p.qpad_coop;
+        k.prof = c.P.dev + c.P.off8;  // the coop kernel reads the int8 profile
+        HIPCHECK(hipStreamWaitEvent(h->side2, h->ev[0], 0));
+        MARK(4, h->side2);
+        HIPCHECK(swk::launch_inter_coop(k, p.ncoop, p.affine, h->opts.coop_skew != 0, h->side2));
+        MARK(5, h->side2);
+        HIPCHECK(hipEventRecord(h->coop_done, h->side2));
         ++h->launches;
-        if (ncoop || nr) HIPCHECK(hipStreamWaitEvent(h->stream, h->coop_done, 0));
-        const bool seen = db->icount_seen && db->seen_key == skey && db->seen_qhash == qhash &&
-                          db->seen_qlen == qlen && db->seen_nr == nr;
-        if (f16 && rescue && !db->icount_pending && !seen) {
-            // the fp16 pass's flagged count and largest flagged block, read
-            // by a later scan (no synchronisation here), after every fp16
-            // launch that appends to list A has joined the main stream
-            if (!db->h_icount) {
-                HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&db->h_icount), 2 * sizeof(int32_t),
-                                       hipHostMallocDefault));
-                HIPCHECK(hipEventCreateWithFlags(&db->icount_ev, hipEventDisableTiming));
-            }
-            HIPCHECK(hipMemcpyAsync(db->h_icount, listA, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-            HIPCHECK(hipMemcpyAsync(db->h_icount + 1, maxA, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-            HIPCHECK(hipEventRecord(db->icount_ev, h->stream));
-            db->icount_pending = true;
-            db->icount_key = skey;
-            db->icount_qlen = qlen;
-            db->icount_nr = nr;
-            db->icount_qhash = qhash;
-        }
-        tail_a = a;
-        inter_tail = rescue && !drain;
-        if (deferred && inter_tail) HIPCHECK(hipEventRecord(h->main_done, h->stream));
-        else if (inter_tail && (rc = launch_inter_tail(h->stream, db->d_bnd_h, db->d_bnd_f))) return rc;
+    } else if (p.nr) {
+        // blocks [0, nr) in int16 by wave pairs beside the fp16 launch;
+        // their near-32767 ones go to list B (the int32 stage)
+        swk::InterArgs k = c.a;
+        k.nblocks = p.nr;
+        k.blk_base = 0;
+        k.blk_first = 0;
+        k.rescue_list = c.listB + 1;
+        k.rescue_count = c.listB;
+        k.rescue_max = nullptr;
+        HIPCHECK(hipEventRecord(h->fork2, h->stream));
+        HIPCHECK(hipStreamWaitEvent(h->side2, h->fork2, 0));
+        MARK(4, h->side2);
+        HIPCHECK(swk::launch_inter_x2p(k, p.affine, false, false, 2, h->side2));
+        MARK(5, h->side2);
+        HIPCHECK(hipEventRecord(h->coop_done, h->side2));
+        ++h->launches;
     }
-    if (deferred && (inter_tail || intra_tail)) {
-        // this scan's rescue tail beside the next scan's fp16 passes
-        if (inter_tail) {
-            HIPCHECK(hipStreamWaitEvent(ts, h->main_done, 0));
-            if ((rc = launch_inter_tail(ts, db->d_rbnd_h, db->d_rbnd_f))) return rc;
-        }
-        if (intra_tail) {
-            HIPCHECK(hipStreamWaitEvent(ts, h->side_done, 0));
-            if ((rc = launch_intra_tail(ts, db->d_rlbnd_h, db->d_rlbnd_f))) return rc;
-        }
-        HIPCHECK(hipEventRecord(h->tail_done[par], ts));
-        h->tail_pending[par] = true;
-        sw_handle::ProfSlot& S = h->prof[P.slot];
-        HIPCHECK(hipEventRecord(S.tail_read, ts));
-        S.tail_pending = true;
+    MARK(6, h->stream);
+    if (p.npair)  // one launch: pairs for blocks [nr, npair), one wave per block after
+        HIPCHECK(swk::launch_inter_x2p(c.a, p.affine, p.f16, true, swplan::pair_group(plan_view(c.db)), h->stream));
+    else
+        HIPCHECK(swk::launch_inter(c.a, p.affine, p.shape, h->stream));
+    MARK(7, h->stream);
+    ++h->launches;
+    if (p.ncoop || p.nr) HIPCHECK(hipStreamWaitEvent(h->stream, h->coop_done, 0));
+    return inter_tail(c);
+}
+
+// The merged launch's drain arguments (swk::DrainArgs): the four rescue
+// stages on the tails' boundary rows, as a device blob (drain_blob).
+int drain_args(Scan& c, const swk::IntraArgs& x, const sw_db::LptTable& t, const swk::DrainArgs** out) {
+    const swplan::ScanPlan& p = c.plan;
+    const RescueStages s = rescue_stages(c, x, tail_rows(c.db), true);
+    swk::DrainArgs d{};
+    d.a16 = s.a16;
+    d.a32 = s.a32;
+    d.i16 = s.i16;
+    d.i32 = s.i32;
+    d.lists[0] = c.listA;
+    d.lists[1] = c.listB;
+    d.lists[2] = c.list1;
+    d.lists[3] = c.list2;
+    d.heads[0] = c.headA;
+    d.heads[1] = c.headA + 1;
+    d.heads[2] = c.head1;
+    d.heads[3] = c.head1 + 1;
+    d.fault = c.h->d_fault;
+    d.spin = c.h->opts.drain_spin >= 0 ? c.h->opts.drain_spin : (1 << 22);
+    // (every field of d the blob's bytes depend on)
+    const std::vector<uint64_t> key = {
+        reinterpret_cast<uint64_t>(c.P.dev), c.P.off8, c.P.off16, c.P.intra_off, static_cast<uint64_t>(c.par),
+        reinterpret_cast<uint64_t>(c.scores), static_cast<uint64_t>(c.qlen), c.skey,
+        static_cast<uint64_t>(p.npair) | static_cast<uint64_t>(c.a.blk_tri) << 32,
+        static_cast<uint64_t>(p.nquad) | static_cast<uint64_t>(p.ntail) << 32,
+        static_cast<uint64_t>(c.P.stride),
+        reinterpret_cast<uint64_t>(c.a.trace),
+        static_cast<uint64_t>(p.ri2) | static_cast<uint64_t>(p.lpt_rows) << 16 | static_cast<uint64_t>(t.npipe) << 32,
+        static_cast<uint64_t>(static_cast<uint32_t>(t.pipe_tail)),
+        static_cast<uint64_t>(static_cast<uint32_t>(d.spin))};
+    return drain_blob(c.db, c.h->stream, key, d, out);
+}
+
+// One launch on the main stream: the inter groups + single waves and the
+// long subjects' fp16 pass, longest work first (sw_scan_lpt); draining, it
+// runs the rescue stages too, else they follow in stream order or deferred.
+int merged_pass(Scan& c) {
+    sw_handle* h = c.h;
+    const swplan::ScanPlan& p = c.plan;
+    int rc;
+    h->had_intra = true;
+    MARK(6, h->stream);
+    const sw_db::LptTable* t = lpt_table(c.db, p);
+    if (!t) return SW_E_HIP;
+    swk::IntraArgs x = c.x;
+    x.pipe_pairs = t->npipe;
+    x.pipe_tail = t->pipe_tail;
+    const swk::DrainArgs* dargs = nullptr;
+    if (p.drain && (rc = drain_args(c, x, *t, &dargs))) return rc;
+    HIPCHECK(swk::launch_scan_lpt(c.a, x, t->d_order, t->n, p.affine, p.ri2, h->cus, h->stream, dargs, c.lpt_next,
+                                  h->opts.lpt_persist >= 2 ? h->opts.lpt_persist : 0, p.lpt_rows));
+    ++h->launches;
+    // (a draining launch ends the scan: its end event is ev[3])
+    if (!p.drain) MARK(7, h->stream);
+    // the fp16 pass's flagged count, as long_pass's
+    if ((rc = readback_record(c.db->lcount, {c.skey, c.qhash, c.qlen, 0}, c.list1, nullptr, h->stream))) return rc;
+    if (!p.drain && (rc = intra_tail(c, h->stream))) return rc;
+    return inter_tail(c);
+}
+
+// A deferred scan's rescue tail beside the next scan's fp16 passes.
+int deferred_tails(Scan& c) {
+    sw_handle* h = c.h;
+    int rc;
+    if (!c.deferred || !(c.inter_tail || c.intra_tail)) return SW_OK;
+    const RescueStages s = rescue_stages(c, c.x, tail_rows(c.db), false);
+    if (c.inter_tail) {
+        HIPCHECK(hipStreamWaitEvent(h->tail, h->main_done, 0));
+        if ((rc = launch_inter_tail(c, h->tail, s))) return rc;
     }
+    if (c.intra_tail) {
+        HIPCHECK(hipStreamWaitEvent(h->tail, h->side_done, 0));
+        if ((rc = launch_intra_tail(c, h->tail, s))) return rc;
+    }
+    HIPCHECK(hipEventRecord(h->tail_done[c.par], h->tail));
+    h->tail_pending[c.par] = true;
+    sw_handle::ProfSlot& S = h->prof[c.P.slot];
+    HIPCHECK(hipEventRecord(S.tail_read, h->tail));
+    S.tail_pending = true;
+    return SW_OK;
+}
+
+// sw_opts rescue_stats: what the guard bands flagged (synchronises).
+int print_rescue_stats(const Scan& c) {
+    sw_handle* h = c.h;
+    const sw_db* db = c.db;
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipStreamSynchronize(h->tail));
+    int32_t cA = 0, cB = 0, l1 = 0, l2 = 0;
+    std::vector<int32_t> ids;
+    if (c.listA) {
+        HIPCHECK(hipMemcpy(&cA, c.listA, 4, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(&cB, c.listB, 4, hipMemcpyDeviceToHost));
+        ids.resize(static_cast<size_t>(cA));
+        if (cA) HIPCHECK(hipMemcpy(ids.data(), c.listA + 1, 4 * ids.size(), hipMemcpyDeviceToHost));
+    }
+    if (c.list1) {
+        HIPCHECK(hipMemcpy(&l1, c.list1, 4, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(&l2, c.list2, 4, hipMemcpyDeviceToHost));
+    }
+    int64_t res = 0;
+    int32_t wmin = 1 << 30, wmax = 0, bmin = 1 << 30, bmax = -1;
+    for (int32_t b : ids) {
+        if (b < 0) continue;  // (taken entries are reset to -1: a drained list shows counts only)
+        res += db->h_blk_res[b];
+        wmin = std::min<int32_t>(wmin, db->h_blk_groups[b] * 16);
+        wmax = std::max<int32_t>(wmax, db->h_blk_groups[b] * 16);
+        bmin = std::min(bmin, b);
+        bmax = std::max(bmax, b);
+    }
+    std::fprintf(stderr,
+                 "rescue: qlen %d go %d ge %d: inter %d/%lld blocks flagged (ids %d..%d, widths %d..%d, "
+                 "%lld of %lld residues), %d again; pairs %d; intra %d/%lld flagged, %d again\n",
+                 c.qlen, c.sc.go, c.sc.ge, cA, static_cast<long long>(db->nblocks), bmin, bmax, wmin, wmax,
+                 static_cast<long long>(res), static_cast<long long>(db->residues), cB, c.plan.npair, l1,
+                 static_cast<long long>(db->nlong), l2);
+    return SW_OK;
+}
+
+// defer: another scan follows on this handle before the caller waits (the
+// queries of a batch but the last): this scan's rescue tail may run on the
+// tail stream beside the next scan's fp16 passes (sw_handle::tail).
+// rq (nullable): rank the scan's scores too (a top-K launch after every
+// stage that writes them, before the scan's end event).
+int scan_impl_body(sw_handle* h, const sw_db* cdb, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
+                   int32_t* scores_dev, bool defer = false, const RankReq* rq = nullptr) {
+    sw_db* db = const_cast<sw_db*>(cdb);
+    if (!h || !db || (!query && qlen > 0) || qlen < 0 || !scores_dev) return fail(SW_E_INVALID, "null argument");
+    if (rq) defer = false;  // the ranking reads every rescued score
+    const int8_t* mat;
+    int go, ge, rc;
+    if ((rc = check_fault(h))) return rc;
+    if ((rc = check_scoring(sc, &mat, &go, &ge))) return rc;
+    if (!db->built && (rc = build_db(db))) return rc;
+    HIPCHECK(hipSetDevice(h->device));
+    h->launches = 0;
+    h->had_intra = false;
+    if ((rc = next_events(h))) return rc;
+    if (qlen == 0) return scan_empty(h, db, scores_dev, defer, rq);
+
+    Scan c;
+    c.h = h;
+    c.db = db;
+    c.qlen = qlen;
+    c.scores = scores_dev;
+    c.sc = swplan::plan_scoring(mat, go, ge);
+    c.skey = 1469598103934665603ull;
+    for (int k = 0; k < 625; ++k) c.skey = (c.skey ^ static_cast<uint8_t>(mat[k])) * 1099511628211ull;
+    c.skey = ((c.skey ^ static_cast<uint32_t>(go)) * 1099511628211ull ^ static_cast<uint32_t>(ge)) * 1099511628211ull;
+    c.qhash = 1469598103934665603ull;
+    for (int32_t k = 0; k < qlen; ++k) c.qhash = (c.qhash ^ query[k]) * 1099511628211ull;
+
+    // The form of the scan: the two adaptive routes from the database's
+    // earlier scans, then the plan; a merged launch drains its own rescue
+    // lists when it gets boundary rows for that.
+    const bool i16_first = adapt_intra_i16_first(db, c.skey, qlen, h->opts.intra_i16_first);
+    const int32_t i16_span = adapt_inter_i16_span(db, c.skey, qlen, h->opts.inter_i16_span);
+    c.plan = swplan::scan_plan(plan_view(db), qlen, c.sc, i16_first, i16_span);
+    if (c.plan.lpt) c.plan.set_drain(ensure_rbnd(db, c.plan.affine, c.plan.intra_x2));
+    const swplan::ScanPlan& p = c.plan;
+    db->last_ncoop = p.ncoop;
+    db->last_npair = p.npair;
+    db->last_pair_merged = p.npair != 0;
+
+    if ((rc = scan_lists(c, defer))) return rc;
+    if ((rc = scan_profiles(c, query, mat))) return rc;
+    if ((rc = scan_args(c))) return rc;
+    if (!p.kernel.empty()) h->last_kernel = p.kernel;
+    h->last_intra = p.intra_kernel;
+    if (p.lpt) {
+        if ((rc = merged_pass(c))) return rc;
+    } else {
+        // fork: the side streams start when the main stream reaches ev[0]
+        // (the merged launch has none: its scan time runs from ev[6])
+        MARK(0, h->stream);
+        if (db->nlong && (rc = long_pass(c))) return rc;
+        MARK(1, db->nlong ? h->side : h->stream);
+        if (db->nblocks && (rc = inter_pass(c))) return rc;
+    }
+    if ((rc = deferred_tails(c))) return rc;
+
+    // join (the merged launch has no separate inter end, nor a side stream
+    // to join), rank, and the end event
     if (!db->nblocks)
         for (int k = 6; k < 8; ++k) MARK(k, h->stream);
-    // (the merged launch has no separate inter end, nor a side stream to join)
-    if (!lpt) MARK(2, h->stream);
-    if (db->nlong && !lpt) HIPCHECK(hipStreamWaitEvent(h->stream, h->ev[1], 0));
+    if (!p.lpt) MARK(2, h->stream);
+    if (db->nlong && !p.lpt) HIPCHECK(hipStreamWaitEvent(h->stream, h->ev[1], 0));
     // the scan completes on the handle's stream: so do earlier deferred tails
-    if (!deferred && (rc = join_tails(h))) return rc;
+    if (!c.deferred && (rc = join_tails(h))) return rc;
     if (rq && (rc = rank_after(h, db, scores_dev, *rq))) return rc;
     MARK(3, h->stream);
     h->open_slot = -1;
     h->evpool[h->nscans - 1].launches = h->launches;
     h->timed = true;
-    if (O.rescue_stats == 1) {  // diagnostics: what the guard bands flagged (synchronises)
-        HIPCHECK(hipStreamSynchronize(h->stream));
-        HIPCHECK(hipStreamSynchronize(h->tail));
-        int32_t cA = 0, cB = 0, l1 = 0, l2 = 0;
-        std::vector<int32_t> ids;
-        if (listA) {
-            HIPCHECK(hipMemcpy(&cA, listA, 4, hipMemcpyDeviceToHost));
-            HIPCHECK(hipMemcpy(&cB, listB, 4, hipMemcpyDeviceToHost));
-            ids.resize(static_cast<size_t>(cA));
-            if (cA) HIPCHECK(hipMemcpy(ids.data(), listA + 1, 4 * ids.size(), hipMemcpyDeviceToHost));
-        }
-        if (list1) {
-            HIPCHECK(hipMemcpy(&l1, list1, 4, hipMemcpyDeviceToHost));
-            HIPCHECK(hipMemcpy(&l2, list2, 4, hipMemcpyDeviceToHost));
-        }
-        int64_t res = 0;
-        int32_t wmin = 1 << 30, wmax = 0, bmin = 1 << 30, bmax = -1;
-        for (int32_t b : ids) {
-            if (b < 0) continue;  // (taken entries are reset to -1: a drained list shows counts only)
-            res += db->h_blk_res[b];
-            wmin = std::min<int32_t>(wmin, db->h_blk_groups[b] * 16);
-            wmax = std::max<int32_t>(wmax, db->h_blk_groups[b] * 16);
-            bmin = std::min(bmin, b);
-            bmax = std::max(bmax, b);
-        }
-        std::fprintf(stderr,
-                     "rescue: qlen %d go %d ge %d: inter %d/%lld blocks flagged (ids %d..%d, widths %d..%d, "
-                     "%lld of %lld residues), %d again; pairs %d; intra %d/%lld flagged, %d again\n",
-                     qlen, go, ge, cA, static_cast<long long>(db->nblocks), bmin, bmax, wmin, wmax,
-                     static_cast<long long>(res), static_cast<long long>(db->residues), cB, npair, l1,
-                     static_cast<long long>(db->nlong), l2);
-    }
-    return SW_OK;
+    return h->opts.rescue_stats == 1 ? print_rescue_stats(c) : SW_OK;
 }
 
 // A scan that fails after its profiles were built leaves the profile slot
@@ -2304,10 +2289,8 @@ int sw_db_free(sw_db* db) {
                 std::fclose(f);
             }
     }
-    if (db->h_lcount) (void)hipHostFree(db->h_lcount);
-    if (db->lcount_ev) (void)hipEventDestroy(db->lcount_ev);
-    if (db->h_icount) (void)hipHostFree(db->h_icount);
-    if (db->icount_ev) (void)hipEventDestroy(db->icount_ev);
+    readback_free(db->lcount);
+    readback_free(db->icount);
     free_dev(db);
     delete db;
     return SW_OK;
@@ -2315,13 +2298,9 @@ int sw_db_free(sw_db* db) {
 
 int sw_db_reset_adaptive(sw_db* db) {
     if (!db) return fail(SW_E_INVALID, "null argument");
-    // a readback still in flight lands in the same pinned words later, in
-    // stream order before any readback a later scan issues: ignoring it is safe
-    db->lcount_pending = false;
-    db->lcount_seen = false;
+    readback_reset(db->lcount);
     db->i16_first.clear();
-    db->icount_pending = false;
-    db->icount_seen = false;
+    readback_reset(db->icount);
     db->i16_span.clear();
     return SW_OK;
 }

@@ -1265,8 +1265,7 @@ static void launch_lpt_t(const InterArgs& a, const IntraArgs& ia, const int32_t*
     }
 }
 
-bool lpt_supported(int ri) { return ri == 4 || ri == 6 || ri == 8; }
-
+// (the rows per lane below: swplan::lpt_supported, sw_plan.cpp, agrees)
 hipError_t launch_scan_lpt(const InterArgs& a, const IntraArgs& ia, const int32_t* order, int n, bool affine, int ri,
                            int cus, hipStream_t s, const DrainArgs* drain, int32_t* next, int loop_grid, int rows) {
     if (n <= 0) return hipSuccess;

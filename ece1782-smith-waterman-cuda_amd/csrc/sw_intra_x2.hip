@@ -17,29 +17,6 @@ __global__ __launch_bounds__(kWavesPerWG * kLanes) void sw_intra_x2(IntraArgs a)
     ix2::intra_x2_wg<RI, F16, LIST, LIN, true, false, kConv>(a, blockIdx.x, img);
 }
 
-int intra_x2_rows_for(int qlen, int longest, int wide, int forced) {
-    // chunks x steps x (cell pairs per lane-step + conveyor/hand-off overhead)
-    if (forced > 0) {  // sw_opts intra_x2_rows (tests: force a shape)
-        const int ri = forced;
-        if (ri == 4 || ri == 6 || ri == 8 || ri == 10 || ri == 12 || ri == 16) return ri;
-        if (ri == kIntraX2MaxRI && wide >= 1) return ri;
-    }
-    int best_ri = 16;
-    double best_cost = 1e300;
-    for (int ri : {4, 6, 8, 10, 12, 16, kIntraX2MaxRI}) {
-        if (ri == kIntraX2MaxRI && wide < 2) continue;
-        const int chunk = kLanes * ri;
-        const int nch = (qlen + chunk - 1) / chunk;
-        // SIMD cycles per lane-step: ri rows x 6.8 ops x 4.25 + ~80 of conveyor
-        const double cost = static_cast<double>(nch) * (longest + kLanes - 1) * (ri * 28.8 + 80.0);
-        if (cost < best_cost) {
-            best_cost = cost;
-            best_ri = ri;
-        }
-    }
-    return best_ri;
-}
-
 template <bool F16, bool LIST, bool LIN>
 static hipError_t launch_intra_x2_t(const IntraArgs& a, int ri, hipStream_t s) {
     const int npairs = (a.nsubj + 1) / 2;

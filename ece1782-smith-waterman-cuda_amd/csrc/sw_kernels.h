@@ -247,13 +247,12 @@ __device__ __forceinline__ int list_claim(int32_t* count, int32_t* head, int wan
 // kernel (int16 profile), f16: its fp16 form.  x2_ok: 2 = the scan is
 // provably int16-safe (any packed kernel may run); 1 = a guarded packed
 // kernel may run (saturating blocks are re-scored at int32); 0 = int32 only.
-// o.int16_guard / o.inter_variant override the choice (tests, A/B).
+// Chosen by swplan::inter_shape (sw_plan.cpp), like the other host policies.
 struct InterShape {
     int R, SG;
     bool x2s = false;
     bool f16 = false;
 };
-InterShape inter_shape(bool affine, int x2_ok, const sw_opts& o);
 // true if the chosen inter kernel may flag blocks for int32 re-scoring
 // (16-bit kernels beyond the static int16 bound).
 inline bool inter_needs_rescue(const InterShape& v, int x2_ok) { return v.f16 || (v.x2s && x2_ok != 2); }
@@ -263,10 +262,6 @@ inline bool inter_has_pair(const InterShape& v) { return v.x2s && v.R == 64 && v
 // (0 = the chosen inter kernel does not use it: one subject per lane with two
 // strips per pass has no long single-wave tail, coop on/off within 1 %).
 inline int inter_coop_divisor(const InterShape& v) { return v.x2s ? 0 : 530000; }
-// Name of the per-wave inter kernel launch_inter() runs, e.g. "sw_inter_x2s<32,8,affine,fp16>".
-const char* inter_kernel_name(const InterShape& v, bool affine);
-// Query rows per lane the intra kernel uses for this query (2..16, even).
-int intra_rows_for(int qlen, int longest);
 // Bytes of one intra profile chunk (64*ri query rows, 32 codes).
 int intra_chunk_bytes(int ri);
 __host__ __device__ constexpr int intra_rip(int RI) { return (RI + 3) / 4 * 4; }
@@ -274,8 +269,9 @@ __host__ __device__ constexpr int intra_rip(int RI) { return (RI + 3) / 4 * 4; }
 hipError_t launch_inter(const InterArgs& a, bool affine, const InterShape& v, hipStream_t s);
 // Wide blocks [0, ncoop): one 4-wave workgroup per block, the waves pipelined
 // over query strips (skew: strip k+1 one sub-group behind strip k).
+// Strips of kCoopRows query rows.
+constexpr int kCoopRows = 32;
 hipError_t launch_inter_coop(const InterArgs& a, int ncoop, bool affine, bool skew, hipStream_t s);
-int inter_coop_rows();
 // One subject per lane, two R-row query strips per pass in the two int16
 // halves (sw_inter_x2.hip); qpad is a multiple of 2R; boundary rows are
 // (H | F << 16) dwords in bnd_h.
@@ -316,7 +312,6 @@ struct DrainArgs {
     int32_t* fault;     // host-mapped word: a claimed entry never appeared (list_wait_take)
     int32_t spin;       // list_wait_take's bound (sw_opts drain_spin)
 };
-bool lpt_supported(int ri);
 // next (nullable; zero at launch): with it, a table of at least 3 rounds of
 // resident workgroups runs one workgroup per resident slot, each taking its
 // next entry of order[] from this counter when it has finished one (the
@@ -347,23 +342,16 @@ constexpr int intra_period(int ri) { return ri == kIntraX2MaxRI ? 16 : 8; }
 constexpr int intra_bias_rows(int ri) { return ri + intra_period(ri) + 2 > 26 ? ri + intra_period(ri) + 2 : 26; }
 
 // int32 re-scoring of the blocks a 16-bit kernel listed (device-side count);
-// strips of rescue_rows(affine) query rows.
-int rescue_rows(bool affine);
+// strips of swplan::rescue_rows(affine) query rows.
 hipError_t launch_inter_rescue(const InterArgs& a, bool affine, hipStream_t s);
 hipError_t launch_intra(const IntraArgs& a, int ri, bool affine, hipStream_t s);
 // Two subjects per wave, packed fp16 (sw_intra_x2.hip); rows per lane 4..16,
-// and 20 when intra_x2_rows_for allows it.
+// and 20 when swplan::intra_x2_rows_for allows it.
 hipError_t launch_intra_x2(const IntraArgs& a, int ri, hipStream_t s);
 // its int16 form over the device-side list a.subj_list / a.list_count
 hipError_t launch_intra_x2_list16(const IntraArgs& a, int ri, hipStream_t s);
 // ... and over every subject (the chain's first stage when fp16 would flag most)
 hipError_t launch_intra_x2_int16(const IntraArgs& a, int ri, hipStream_t s);
-// wide: 0 = rows per lane 4..16; 1 = 20 too when forced (sw_opts
-// intra_x2_rows, > 0: a forced shape); 2 = 20 by the cost model too.  The host allows 20 only
-// where no merged launch can take the scan (no inter blocks) and the fp16
-// bias of row 19 fits, and picks it only for affine gaps (the linear cell
-// lost 35 % at 20 on C5: its cheaper steps need the third wave per SIMD).
-int intra_x2_rows_for(int qlen, int longest, int wide, int forced);
 
 // Traceback of chosen hits (sw_align.hip): cpu.cpp's tie rules for a linear
 // gap (gap == gap_extend), this build's extension of them for affine gaps.

@@ -39,9 +39,6 @@
 #include "sw_int32.h"
 #include "sw_kernels.h"
 
-#include <cstdio>
-#include <cstdlib>
-
 namespace swk {
 
 template <int R, int SG, bool AFFINE, bool SKEW>
@@ -171,9 +168,6 @@ __global__ __launch_bounds__(256) void sw_inter_coop(InterArgs a) {
     }
 }
 
-constexpr int kCoopRows = 32;
-int inter_coop_rows() { return kCoopRows; }
-
 hipError_t launch_inter_coop(const InterArgs& a, int ncoop, bool affine, bool sk, hipStream_t s) {
     if (ncoop <= 0 || a.qpad <= 0) return hipSuccess;
     const dim3 grid(ncoop), block(kWavesPerWG * kLanes);
@@ -202,50 +196,7 @@ __global__ __launch_bounds__(64) void sw_intra(IntraArgs a) {
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-// Inter-kernel shape (sw_kernels.h InterShape); o.inter_variant "RxSG"
-// overrides (tuning only).
-InterShape inter_shape(bool affine, int x2_ok, const sw_opts& o) {
-    // measured on MI355X (scripts/tune_inter.py, profiles/r01_tune_inter*.jsonl,
-    // r01_x2s/): int16-safe scans (the common case) run the packed two-strips-
-    // per-lane kernel sw_inter_x2s, one subject per lane, in its fp16 form
-    // (biased cell, v_pk_maximum3_f16; C2 affine 9.4 TCUPS vs 6.25 int16),
-    // always guarded (rescue chain fp16 -> int16 -> int32).  Otherwise int32:
-    // affine 32x8, linear 64x8 (+ the cooperative kernel for wide blocks).
-    // Beyond the static int16 bound the packed kernel runs guarded (blocks
-    // reaching kSat16 are re-scored at int32); o.int16_guard = 0 disables that.
-    // (Measured slower and removed in round 2: 16-bit-value and int32-profile
-    // one-subject kernels, pair-table packing, two subjects per lane, the
-    // column-skewed int32 kernel; their numbers are in profiles/r01_tune_*.)
-    const bool y_ok = x2_ok == 2 || (x2_ok == 1 && o.int16_guard != 0);
-    InterShape v = y_ok ? InterShape{64, 8, true, true} : InterShape{affine ? 32 : 64, 8};
-    // o.inter_variant (tests / A-B only): "RxSG" int32 (32x8, 64x8),
-    // "y32x8" the int16 two-strips kernel, "f32x8" / "f32x4" its fp16 form
-    if (const char* e = o.inter_variant; e[0]) {
-        int r = 0, g = 0;
-        if (std::sscanf(e, "f%dx%d", &r, &g) == 2 && y_ok && r == 32 && (g == 8 || (g == 4 && affine)))
-            v = InterShape{2 * r, g, true, true};
-        else if (std::sscanf(e, "y%dx%d", &r, &g) == 2 && y_ok && r == 32 && g == 8)
-            v = InterShape{2 * r, g, true, false};  // R = rows per pass
-        else if (std::sscanf(e, "%dx%d", &r, &g) == 2 && g == 8 && (r == 32 || r == 64))
-            v = InterShape{r, g};
-    }
-    return v;
-}
-
-const char* inter_kernel_name(const InterShape& v, bool affine) {
-    if (v.x2s) {
-        static thread_local char b2[64];
-        std::snprintf(b2, sizeof b2, "sw_inter_x2s<%d,%d,%s%s>", v.R / 2, v.SG, affine ? "affine" : "linear",
-                      v.f16 ? ",fp16" : "");
-        return b2;
-    }
-    static thread_local char buf[96];
-    std::snprintf(buf, sizeof buf, "sw_inter<%d,%d,%s>", v.R, v.SG, affine ? "affine" : "linear");
-    return buf;
-}
-
 // int32 re-scoring of the blocks a 16-bit kernel put on the rescue list.
-int rescue_rows(bool affine) { return affine ? 32 : 64; }
 hipError_t launch_inter_rescue(const InterArgs& a, bool affine, hipStream_t s) {
     // A few hundred waves walk the device-side list; an empty list costs one
     // tiny launch and no host synchronisation.
@@ -254,22 +205,6 @@ hipError_t launch_inter_rescue(const InterArgs& a, bool affine, hipStream_t s) {
     else
         hipLaunchKernelGGL((sw_inter<64, 8, false, false>), dim3(64), dim3(kWavesPerWG * kLanes), 0, s, a);
     return hipGetLastError();
-}
-
-// Rows per lane for the intra kernel: minimise
-//   chunks * (steps per chunk) * (ops per step)
-// with ops per step ~ RI * 3.7 (cells) + 8 (hand-off overhead); RI is even
-// and at most 16 (register budget).
-int intra_rows_for(int qlen, int longest) {
-    int best_ri = 16;
-    double best_cost = 1e300;
-    for (int ri = 2; ri <= 16; ri += 2) {
-        const int chunk = kLanes * ri;
-        const int nch = (qlen + chunk - 1) / chunk;
-        const double cost = static_cast<double>(nch) * (longest + kLanes - 1) * (ri * 3.7 + 8.0);
-        if (cost < best_cost) { best_cost = cost; best_ri = ri; }
-    }
-    return best_ri;
 }
 
 int intra_chunk_bytes(int ri) { return kProfileRows * kLanes * intra_rip(ri); }

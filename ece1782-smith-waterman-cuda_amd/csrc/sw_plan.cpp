@@ -5,17 +5,22 @@
 // longest-first work table of the merged launch (sw_scan_lpt) with its
 // duration estimates.  Plain host code over a read-only view of a database
 // (PlanDb); sw_capi.cpp owns the databases, caches the tables and uploads
-// them.
+// them.  scan_plan (at the end) puts the policies together: the form one
+// scan takes, as a pure function of the database view, the query length,
+// the scoring and the two adaptive routes.
 #include "sw_plan.h"
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <utility>
 #include <vector>
 
-#include "sw_kernels.h"
-
 namespace swplan {
+
+namespace {
+int32_t round_up(int64_t v, int64_t m) { return static_cast<int32_t>((v + m - 1) / m * m); }
+}  // namespace
 
 // Subjects longer than this go to the wavefront kernel.  A 64-lane block of
 // the inter kernel takes time proportional to its longest subject, so very
@@ -313,6 +318,233 @@ LptPlan lpt_plan(const PlanDb& db, int32_t qpad, int rows, int32_t qpad_intra, i
     out.npipe = static_cast<int32_t>(npipe);
     out.pipe_tail = static_cast<int32_t>(pipe_tail);
     return out;
+}
+
+// ---- kernel shapes ---------------------------------------------------------
+// Inter-kernel shape (sw_kernels.h InterShape); o.inter_variant "RxSG"
+// overrides (tuning only).
+swk::InterShape inter_shape(bool affine, int x2_ok, const sw_opts& o) {
+    using swk::InterShape;
+    // measured on MI355X (scripts/tune_inter.py, profiles/r01_tune_inter*.jsonl,
+    // r01_x2s/): int16-safe scans (the common case) run the packed two-strips-
+    // per-lane kernel sw_inter_x2s, one subject per lane, in its fp16 form
+    // (biased cell, v_pk_maximum3_f16; C2 affine 9.4 TCUPS vs 6.25 int16),
+    // always guarded (rescue chain fp16 -> int16 -> int32).  Otherwise int32:
+    // affine 32x8, linear 64x8 (+ the cooperative kernel for wide blocks).
+    // Beyond the static int16 bound the packed kernel runs guarded (blocks
+    // reaching kSat16 are re-scored at int32); o.int16_guard = 0 disables that.
+    // (Measured slower and removed in round 2: 16-bit-value and int32-profile
+    // one-subject kernels, pair-table packing, two subjects per lane, the
+    // column-skewed int32 kernel; their numbers are in profiles/r01_tune_*.)
+    const bool y_ok = x2_ok == 2 || (x2_ok == 1 && o.int16_guard != 0);
+    InterShape v = y_ok ? InterShape{64, 8, true, true} : InterShape{affine ? 32 : 64, 8};
+    // o.inter_variant (tests / A-B only): "RxSG" int32 (32x8, 64x8),
+    // "y32x8" the int16 two-strips kernel, "f32x8" / "f32x4" its fp16 form
+    if (const char* e = o.inter_variant; e[0]) {
+        int r = 0, g = 0;
+        if (std::sscanf(e, "f%dx%d", &r, &g) == 2 && y_ok && r == 32 && (g == 8 || (g == 4 && affine)))
+            v = InterShape{2 * r, g, true, true};
+        else if (std::sscanf(e, "y%dx%d", &r, &g) == 2 && y_ok && r == 32 && g == 8)
+            v = InterShape{2 * r, g, true, false};  // R = rows per pass
+        else if (std::sscanf(e, "%dx%d", &r, &g) == 2 && g == 8 && (r == 32 || r == 64))
+            v = InterShape{r, g};
+    }
+    return v;
+}
+
+std::string inter_kernel_name(const swk::InterShape& v, bool affine) {
+    char b[96];
+    if (v.x2s)
+        std::snprintf(b, sizeof b, "sw_inter_x2s<%d,%d,%s%s>", v.R / 2, v.SG, affine ? "affine" : "linear",
+                      v.f16 ? ",fp16" : "");
+    else
+        std::snprintf(b, sizeof b, "sw_inter<%d,%d,%s>", v.R, v.SG, affine ? "affine" : "linear");
+    return b;
+}
+
+// int32 re-scoring of the blocks a 16-bit kernel put on the rescue list
+// (launch_inter_rescue: sw_inter<32,8,affine> / <64,8,linear>).
+int rescue_rows(bool affine) { return affine ? 32 : 64; }
+
+// Rows per lane for the intra kernel: minimise
+//   chunks * (steps per chunk) * (ops per step)
+// with ops per step ~ RI * 3.7 (cells) + 8 (hand-off overhead); RI is even
+// and at most 16 (register budget).
+int intra_rows_for(int qlen, int longest) {
+    int best_ri = 16;
+    double best_cost = 1e300;
+    for (int ri = 2; ri <= 16; ri += 2) {
+        const int chunk = swk::kLanes * ri;
+        const int nch = (qlen + chunk - 1) / chunk;
+        const double cost = static_cast<double>(nch) * (longest + swk::kLanes - 1) * (ri * 3.7 + 8.0);
+        if (cost < best_cost) { best_cost = cost; best_ri = ri; }
+    }
+    return best_ri;
+}
+
+int intra_x2_rows_for(int qlen, int longest, int wide, int forced) {
+    // chunks x steps x (cell pairs per lane-step + conveyor/hand-off overhead)
+    if (forced > 0) {  // sw_opts intra_x2_rows (tests: force a shape)
+        const int ri = forced;
+        if (ri == 4 || ri == 6 || ri == 8 || ri == 10 || ri == 12 || ri == 16) return ri;
+        if (ri == swk::kIntraX2MaxRI && wide >= 1) return ri;
+    }
+    int best_ri = 16;
+    double best_cost = 1e300;
+    for (int ri : {4, 6, 8, 10, 12, 16, swk::kIntraX2MaxRI}) {
+        if (ri == swk::kIntraX2MaxRI && wide < 2) continue;
+        const int chunk = swk::kLanes * ri;
+        const int nch = (qlen + chunk - 1) / chunk;
+        // SIMD cycles per lane-step: ri rows x 6.8 ops x 4.25 + ~80 of conveyor
+        const double cost = static_cast<double>(nch) * (longest + swk::kLanes - 1) * (ri * 28.8 + 80.0);
+        if (cost < best_cost) {
+            best_cost = cost;
+            best_ri = ri;
+        }
+    }
+    return best_ri;
+}
+
+// The rows per lane sw_scan_lpt is instantiated for: must agree with the
+// switch at the end of launch_scan_lpt (sw_inter_x2.hip), which fails on
+// any other.
+bool lpt_supported(int ri) { return ri == 4 || ri == 6 || ri == 8; }
+
+// ---- the form of a scan ----------------------------------------------------
+PlanScoring plan_scoring(const int8_t* m, int go, int ge) {
+    PlanScoring s;
+    s.go = go;
+    s.ge = ge;
+    for (int k = 0; k < 625; ++k) {
+        s.max_s = std::max<int>(s.max_s, m[k]);
+        // The linear kernels keep S + gap in an int8 profile
+        if (m[k] + go > 127) s.biased_fits = false;
+    }
+    return s;
+}
+
+ScanPlan scan_plan(const PlanDb& db, int32_t qlen, const PlanScoring& s, bool intra_i16_first, int32_t i16_span) {
+    const sw_opts& O = *db.opts;
+    const int max_s = s.max_s, go = s.go, ge = s.ge;
+    ScanPlan p;
+    // If S + gap does not fit the linear kernels' int8 profile, score with
+    // the affine kernels (open == extend is the same DP).
+    p.affine = go != ge || !s.biased_fits;
+    const bool affine = p.affine;
+    // The packed int16 kernel is exact when no H, E, F or H_diag + S can
+    // leave int16: H <= qlen * max S, plus one profile entry (+ gap bias).
+    // Beyond that bound the two-strips kernel runs guarded (saturating lanes
+    // flag their block for int32 re-scoring) as long as one cell's increment
+    // stays far inside the guard band (kSat16 leaves 1152).
+    // Affine 16-bit scans run the fp16 biased cell first; its values sit up
+    // to 26 ge above the true ones, so absurd gap / matrix scales (far beyond
+    // any published scheme) go straight to int32.
+    const bool f16_fits = 2 * max_s + 27 * ge + go < 1024;
+    p.x2_ok = !f16_fits                                                   ? 0
+              : (static_cast<int64_t>(qlen) + 2) * (max_s + go) < 32767 ? 2
+              : (max_s + go < 1000 && ge < 1000)                       ? 1
+                                                                       : 0;
+    p.shape = inter_shape(affine, p.x2_ok, O);
+    const int R = p.shape.R;
+    // int32 re-scoring of blocks a 16-bit kernel flags near saturation
+    p.rescue = swk::inter_needs_rescue(p.shape, p.x2_ok);
+    p.f16 = p.shape.f16;
+    p.qpad_rescue = p.rescue ? round_up(qlen, rescue_rows(affine)) : 0;
+    // fp16 chain stage 2 (the int16 two-strips 32x8 kernel): 64-row passes
+    // (the linear list kernel is the 48x4 shape: 96-row passes)
+    const int list_rows = affine ? 64 : 96;
+    p.qpad_list = p.f16 ? round_up(qlen, list_rows) : 0;
+
+    // Long subjects: two per wave in packed fp16 (sw_intra_x2) when the guard
+    // applies, with the int32 sw_intra re-scoring the subjects it flags
+    // (sw_opts intra_x2 = 0: int32 only).
+    p.intra_x2 = db.nlong && p.x2_ok >= 1 && O.intra_x2 != 0;
+    p.intra_i16_first = intra_i16_first && p.intra_x2;
+    // (20 rows per lane only where no merged launch can take the scan: no
+    // inter blocks; where the fp16 bias of row 19 fits, as f16_fits; and by
+    // the cost model for affine gaps only, see intra_x2_rows_for)
+    const bool ri2_wide =
+        db.nblocks == 0 && 2 * max_s + (swk::intra_bias_rows(swk::kIntraX2MaxRI) + 1) * ge + go < 1024;
+    const int ri2_model =
+        p.intra_x2 ? intra_x2_rows_for(qlen, db.long_max, ri2_wide ? (affine ? 2 : 1) : 0, O.intra_x2_rows) : 0;
+    // Affine scans with inter blocks take the merged launch (intra rows 4, 6
+    // or 8 only) even where the cost model prefers more rows per lane for the
+    // long subjects alone: its tail pairs and looped grid win more (C3's long
+    // queries at 8 rows: +1.3 %; under linear gaps the wider form stays,
+    // -6.9 % at 8 rows: profiles/r05_ab/c3_ri8/).  A scan that does not take
+    // the merged launch after all keeps the cost model's rows.
+    const int ri2_lpt = (affine && ri2_model > 8 && db.nblocks && O.intra_x2_rows < 0) ? 8 : ri2_model;
+
+    // two-strips scans: the widest blocks by wave pairs (at least two passes);
+    // else the widest blocks first, one cooperative workgroup each (int32,
+    // int8-profile paths)
+    p.npair = (db.nblocks && swk::inter_has_pair(p.shape) && round_up(qlen, R) > R) ? pair_blocks(db) : 0;
+    p.ncoop = (!p.npair && db.nblocks) ? coop_blocks(db, swk::inter_coop_divisor(p.shape)) : 0;
+    p.qpad_coop = p.ncoop ? round_up(qlen, swk::kCoopRows) : 0;
+    // the widest blocks the int16 kernel takes first (adapt_inter_i16_span)
+    p.nr = (p.f16 && p.rescue && p.npair && !p.ncoop) ? i16_span : 0;
+
+    // One merged launch for the fp16 scan, longest work first (sw_scan_lpt):
+    // the inter groups + single waves and the long subjects' fp16 pass, when
+    // the scan takes exactly that shape.  Measured (profiles/r02_strong/lpt/,
+    // r02_round/): C2's 1/8 share 1.92 -> 1.45 ms, 1/4 2.57 -> 2.29.  On the
+    // whole C2 database it was 2 % slower than two concurrent launches until
+    // the launch drained its own rescue lists (no rescue launches or events
+    // after it): now 7.19 -> 7.12 ms under affine scoring (C3 and C4's share
+    // unchanged), but under linear gaps 4.57 -> 5.03 ms (profiles/r04_*/);
+    // since round 5's tail pairs, looped grid and 96-row linear passes the
+    // whole C2 database under linear gaps too: 16,512 -> 16,777 GCUPS
+    // (profiles/r05_ab/lpt_linear_c2/).  Every scan of that shape takes it;
+    // sw_opts lpt 0 / 1 forces either form.
+    const bool lpt_want = O.lpt >= 0 ? O.lpt == 1 : true;
+    p.lpt = lpt_want && db.nlong && db.nblocks && p.intra_x2 && !p.intra_i16_first && p.f16 && p.rescue &&
+            p.npair && !p.ncoop && i16_span == 0 && lpt_supported(ri2_lpt);
+    // The merged launch under linear gaps runs 96-row passes (48-row strips):
+    // its widest blocks' wave groups need fewer rounds (a 375-aa query: 4
+    // passes, one round of a quad, against 6 passes and two rounds of 64
+    // rows), and the share's span is those blocks' latency;
+    // the linear cell's registers leave room for the taller strips.  Affine
+    // scans keep 64 rows (their E column would not fit).  sw_opts lpt_rows.
+    p.lpt_rows = (p.lpt && !affine && O.lpt_rows != 64 && round_up(qlen, 96) > 96) ? 96 : 64;
+    p.qpad_inter = round_up(qlen, p.lpt_rows == 96 ? 96 : R);
+    if (p.lpt) {
+        const int passes = p.qpad_inter / p.lpt_rows;
+        // (tri_width takes precedence: where tris apply, quad_width is not consulted)
+        p.ntri = affine ? lpt_tri_blocks(db, p.npair, passes) : 0;
+        p.nquad = p.ntri ? p.ntri : lpt_quad_blocks(db, p.npair);
+        p.ntail = lpt_tail_blocks(db, p.npair, passes);
+    }
+
+    p.ri = db.nlong ? intra_rows_for(qlen, db.long_max) : 0;
+    p.qpad_intra = p.ri ? round_up(qlen, static_cast<int64_t>(swk::kLanes) * p.ri) : 0;
+    p.ri2 = p.lpt ? ri2_lpt : ri2_model;
+    p.qpad_intra2 = p.ri2 ? round_up(qlen, static_cast<int64_t>(swk::kLanes) * p.ri2) : 0;
+    p.multi_inter = p.qpad_inter > R || p.qpad_rescue > rescue_rows(affine) || p.qpad_coop > swk::kCoopRows ||
+                    p.qpad_list > list_rows;
+    p.multi_intra = (p.ri && p.qpad_intra > swk::kLanes * p.ri) || (p.ri2 && p.qpad_intra2 > swk::kLanes * p.ri2);
+
+    if (db.nblocks) {
+        p.kernel = inter_kernel_name(p.shape, affine);
+        if (p.npair) p.kernel.replace(0, sizeof("sw_inter_x2s") - 1, "sw_inter_x2p");     // + wave pairs
+        if (p.lpt_rows == 96) p.kernel.replace(p.kernel.find("<32,"), 4, "<48,");  // 48-row strips
+        if (p.nr) p.kernel += "+int16[0," + std::to_string(p.nr) + ")";
+        if (p.ntail) p.kernel += "+tail" + std::to_string(p.ntail);
+        if (p.ntri) p.kernel += "+tri" + std::to_string(p.ntri);
+        if (p.lpt) p.kernel += "+lpt";
+    }
+    p.intra_kernel = !db.nlong   ? "none"
+                     : p.intra_x2 ? "sw_intra_x2<" + std::to_string(p.ri2) + (p.intra_i16_first ? ",int16>" : ">")
+                                  : "sw_intra<" + std::to_string(p.ri) + (affine ? ",affine>" : ",linear>");
+    return p;
+}
+
+void ScanPlan::set_drain(bool got_rows) {
+    if (!lpt || !got_rows || drain) return;
+    drain = true;
+    ri = ri2;
+    qpad_intra = qpad_intra2;  // the same rows per lane
+    multi_intra = qpad_intra > swk::kLanes * ri;
+    kernel += "+drain";
 }
 
 }  // namespace swplan

@@ -1,14 +1,19 @@
 // sw_plan.h — the host driver's scan-planning policies (sw_plan.cpp): plain
 // functions of a read-only database view, so the policies and the merged
 // launch's work table can be built and checked without a GPU
-// (tests/test_plan.py).  sw_capi.cpp owns the databases and the device
-// copies of the tables.
+// (tests/test_plan.py).  scan_plan() is where the form of a scan is decided:
+// gap model, kernel shapes, rows per lane, block counts, merged launch or
+// not, and the names sw_last_kernel reports; sw_capi.cpp's scan_impl_body
+// only enqueues what the plan says.  sw_capi.cpp owns the databases and the
+// device copies of the tables.
 #pragma once
 
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "sw_amd.h"
+#include "sw_kernels.h"
 
 namespace swplan {
 
@@ -19,6 +24,7 @@ struct PlanDb {
     int64_t nblocks = 0;                  // 64-subject inter blocks
     int64_t nlong = 0;                    // long subjects (the wavefront kernel's)
     int32_t long_threshold = 0;
+    int32_t long_max = 0;                 // the longest long subject
     const uint32_t* blk_groups = nullptr;  // [nblocks] 16-column groups per block, widest first
     const int32_t* llen = nullptr;         // [nlong] long subjects' lengths, longest first
     const sw_opts* opts = nullptr;         // the handle's kernel-form overrides
@@ -43,6 +49,74 @@ int32_t lpt_tail_blocks(const PlanDb& db, int32_t npair, int passes);
 double intra_step_us(int ri);
 double single_ticks(int64_t ncols, int passes);
 double group_ticks_host(int64_t ncols, int passes, int G);
+
+// Shape of the inter kernel for this gap model (swk::InterShape; x2_ok as
+// ScanPlan's); o.int16_guard / o.inter_variant override the choice (tests, A/B).
+swk::InterShape inter_shape(bool affine, int x2_ok, const sw_opts& o);
+// Name of the per-wave inter kernel launch_inter() runs, e.g. "sw_inter_x2s<32,8,affine,fp16>".
+std::string inter_kernel_name(const swk::InterShape& v, bool affine);
+// Query rows per strip of the int32 re-scoring of listed blocks (launch_inter_rescue).
+int rescue_rows(bool affine);
+// Query rows per lane the int32 intra kernel uses for this query (2..16, even).
+int intra_rows_for(int qlen, int longest);
+// ... and the two-subjects fp16 one.  wide: 0 = rows per lane 4..16; 1 = 20
+// too when forced (sw_opts intra_x2_rows, > 0: a forced shape); 2 = 20 by the
+// cost model too.  scan_plan allows 20 only where no merged launch can take
+// the scan (no inter blocks) and the fp16 bias of row 19 fits, and picks it
+// only for affine gaps (the linear cell lost 35 % at 20 on C5: its cheaper
+// steps need the third wave per SIMD).
+int intra_x2_rows_for(int qlen, int longest, int wide, int forced);
+// Rows per lane the merged launch is built for.
+bool lpt_supported(int ri);
+
+// What a scan's form depends on of its scoring.
+struct PlanScoring {
+    int max_s = 0;            // the matrix's largest entry (at least 0)
+    int go = 0, ge = 0;
+    bool biased_fits = true;  // matrix + gap fits the linear kernels' int8 profile
+};
+PlanScoring plan_scoring(const int8_t* matrix625, int go, int ge);
+
+// The form of one scan (qlen > 0): everything sw_capi.cpp's enqueue stages
+// read.  Final when scan_plan returns, but for set_drain.
+struct ScanPlan {
+    bool affine = false;    // the affine kernels (go != ge, or the biased profile does not fit)
+    // 2 = provably int16-safe (any packed kernel may run); 1 = a guarded
+    // packed kernel may run (saturating blocks re-scored at int32); 0 = int32 only
+    int x2_ok = 0;
+    swk::InterShape shape{};
+    bool rescue = false;    // the inter kernel may flag blocks for re-scoring
+    bool f16 = false;       // ... in its fp16 form (rescue chain fp16 -> int16 -> int32)
+    bool intra_x2 = false;  // long subjects two per wave in fp16 first
+    bool intra_i16_first = false;  // ... or in int16 first (the adaptive route, where intra_x2)
+    int ri = 0;             // rows per lane: the int32 long-subject kernel
+    int ri2 = 0;            // ... and the fp16 / int16 one
+    // the query padded to each kernel's pass height (0: the kernel does not run)
+    int32_t qpad_inter = 0, qpad_intra = 0, qpad_intra2 = 0, qpad_rescue = 0, qpad_list = 0, qpad_coop = 0;
+    int32_t npair = 0;      // widest blocks by wave groups
+    int32_t ncoop = 0;      // ... or by the cooperative int32 kernel
+    int32_t nr = 0;         // widest blocks in int16 beside the fp16 launch (the span used)
+    bool lpt = false;       // one merged launch (sw_scan_lpt)
+    bool drain = false;     // ... that re-scores what it flags itself (set_drain)
+    int lpt_rows = 64;      // its query rows per pass: 64, or 96 under linear gaps
+    int32_t ntri = 0, nquad = 0, ntail = 0;  // its 3-wave groups, quads (= ntri when tris run), tail pairs
+    bool multi_inter = false, multi_intra = false;  // more than one pass: boundary rows needed
+    // what sw_last_kernel / sw_last_intra_kernel report; kernel is empty
+    // when no inter kernel runs (the handle keeps the last scan's name),
+    // intra_kernel "none" without long subjects
+    std::string kernel, intra_kernel;
+
+    // The one runtime fact the plan cannot know: whether the merged launch
+    // obtained boundary rows of its own (sw_capi.cpp ensure_rbnd; lpt only).
+    // With them it drains its rescue lists itself, the int32 long-subject
+    // stage at the fp16 form's rows per lane: ri = ri2, qpad_intra (and
+    // multi_intra, a function of the two) follow, the name gets "+drain".
+    void set_drain(bool got_rows);
+};
+
+// intra_i16_first, i16_span: the adaptive routes (sw_capi.cpp
+// adapt_intra_i16_first, adapt_inter_i16_span; span within 0 .. nblocks).
+ScanPlan scan_plan(const PlanDb& db, int32_t qlen, const PlanScoring& s, bool intra_i16_first, int32_t i16_span);
 
 // The merged launch's work table: entries longest (estimated) first.  An
 // entry >= 0 is an inter workgroup of x2p_wg's numbering (groups, then

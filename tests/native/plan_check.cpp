@@ -4,11 +4,14 @@
 // every inter block and every long-subject pair is scanned by exactly one
 // entry, whatever mix of quads / tri groups with spare waves / pairs /
 // single waves / tail pairs and pipelined pairs the policies choose, and the
-// table is sorted longest first.  Built and run by tests/test_plan.py.
+// table is sorted longest first.  And of the form of a scan (sw_plan.cpp
+// scan_plan): the conditions every plan meets, and the forms of the scans
+// whose routing is known.  Built and run by tests/test_plan.py.
 #include <cstdio>
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "sw_kernels.h"
@@ -111,9 +114,178 @@ static sw_opts policy_defaults() {
     std::memset(&o, 0, sizeof o);
     o.size = static_cast<int32_t>(sizeof o);
     for (int32_t* f : {&o.lpt_pipe, &o.quad_width, &o.pair_width, &o.pair_group, &o.coop_width, &o.tail_pairs,
-                       &o.tri_width, &o.lpt_pipe_tail})
+                       &o.tri_width, &o.lpt_pipe_tail, &o.lpt, &o.lpt_rows, &o.intra_x2, &o.intra_x2_rows,
+                       &o.int16_guard})
         *f = -1;
     return o;
+}
+
+// ---- the form of a scan (sw_plan.cpp scan_plan) ----------------------------
+// A database view of scenario()'s kind: nb blocks of widths wmax .. wmin,
+// nlong long subjects of lengths lmax .. lmax / 2, long above `threshold`.
+struct Shape {
+    std::vector<uint32_t> groups;
+    std::vector<int32_t> llen;
+    sw_opts o;
+    swplan::PlanDb db;
+    Shape(int64_t nb, int wmax, int wmin, int64_t nlong, int lmax, int threshold, const sw_opts& opts)
+        : groups(nb), llen(nlong), o(opts) {
+        for (int64_t b = 0; b < nb; ++b)
+            groups[b] = static_cast<uint32_t>((wmax - (wmax - wmin) * b / (nb > 1 ? nb - 1 : 1) + 15) / 16);
+        for (int64_t k = 0; k < nlong; ++k)
+            llen[k] = static_cast<int32_t>(lmax - (lmax / 2) * k / (nlong > 1 ? nlong - 1 : 1));
+        db.n = nb * 64 + nlong;
+        db.residues = db.n * 300;
+        db.nblocks = nb;
+        db.nlong = nlong;
+        db.long_threshold = threshold;
+        db.long_max = nlong ? lmax : 0;
+        db.blk_groups = groups.data();
+        db.llen = llen.data();
+        db.opts = &o;
+        db.cus = 256;
+    }
+    Shape(const Shape&) = delete;
+};
+
+static bool has(const std::string& s, const char* part) { return s.find(part) != std::string::npos; }
+
+// The plan of one scan, after the conditions every plan meets.
+static swplan::ScanPlan plan(const char* name, const Shape& sh, int qlen, int max_s, int go, int ge,
+                             bool i16_first = false, int32_t span = 0) {
+    swplan::PlanScoring s;
+    s.max_s = max_s;
+    s.go = go;
+    s.ge = ge;
+    s.biased_fits = max_s + go <= 127;
+    const swplan::ScanPlan p = swplan::scan_plan(sh.db, qlen, s, i16_first, span);
+    // every padded length is a multiple of its kernel's pass height and holds the query
+    const int heights[6][2] = {{p.qpad_inter, p.lpt_rows == 96 ? 96 : p.shape.R},
+                               {p.qpad_intra, 64 * p.ri},
+                               {p.qpad_intra2, 64 * p.ri2},
+                               {p.qpad_rescue, swplan::rescue_rows(p.affine)},
+                               {p.qpad_list, p.affine ? 64 : 96},
+                               {p.qpad_coop, swk::kCoopRows}};
+    for (int k = 0; k < 6; ++k) {
+        const int q = heights[k][0], rows = heights[k][1];
+        if (q == 0 && k != 0) continue;  // the kernel does not run
+        CHECK(rows > 0 && q % rows == 0 && q >= qlen, "%s: padded length %d: %d for %d rows, qlen %d", name, k, q, rows, qlen);
+    }
+    CHECK((p.ri != 0) == (sh.db.nlong != 0), "%s: ri %d with %lld long subjects", name, p.ri, (long long)sh.db.nlong);
+    CHECK((p.ri2 != 0) == p.intra_x2, "%s: ri2 %d, intra_x2 %d", name, p.ri2, p.intra_x2);
+    CHECK((p.qpad_rescue != 0) == p.rescue && (p.qpad_list != 0) == p.f16 && (p.qpad_coop != 0) == (p.ncoop != 0),
+          "%s: a padded length without its kernel", name);
+    CHECK(!p.drain, "%s: draining before set_drain", name);
+    if (p.lpt) {
+        CHECK(p.npair > 0 && p.ncoop == 0 && p.nr == 0, "%s: lpt with npair %d ncoop %d nr %d", name, p.npair, p.ncoop, p.nr);
+        CHECK(p.ri2 == 4 || p.ri2 == 6 || p.ri2 == 8, "%s: lpt with ri2 %d", name, p.ri2);
+        CHECK(p.nquad <= p.npair && p.ntail < sh.db.nblocks - p.npair + (p.ntail == 0), "%s: lpt block ranges", name);
+    } else {
+        CHECK(!p.ntri && !p.nquad && !p.ntail && p.lpt_rows == 64, "%s: merged-launch fields without lpt", name);
+    }
+    CHECK(has(p.kernel, "+lpt") == p.lpt, "%s: name %s, lpt %d", name, p.kernel.c_str(), p.lpt);
+    CHECK((p.lpt_rows == 96) == (p.lpt && !p.affine && qlen > 96), "%s: %d-row passes", name, p.lpt_rows);
+    CHECK(has(p.kernel, "<48,") == (p.lpt_rows == 96), "%s: name %s, %d-row passes", name, p.kernel.c_str(), p.lpt_rows);
+    CHECK(!p.ntri || (p.affine && p.nquad == p.ntri), "%s: ntri %d, affine %d, nquad %d", name, p.ntri, p.affine, p.nquad);
+    CHECK(p.kernel.empty() == (sh.db.nblocks == 0), "%s: inter name '%s'", name, p.kernel.c_str());
+    CHECK((p.intra_kernel == "none") == (sh.db.nlong == 0), "%s: intra name '%s'", name, p.intra_kernel.c_str());
+    // set_drain: the int32 long-subject stage at the fp16 form's rows, the name's suffix, nothing else
+    swplan::ScanPlan d = p;
+    d.set_drain(true);
+    CHECK(d.drain == p.lpt, "%s: set_drain(true) drains %d, lpt %d", name, d.drain, p.lpt);
+    if (d.drain) {
+        CHECK(d.ri == d.ri2 && d.qpad_intra == d.qpad_intra2, "%s: drain ri %d ri2 %d", name, d.ri, d.ri2);
+        CHECK(d.kernel == p.kernel + "+drain", "%s: drain name %s", name, d.kernel.c_str());
+        d.ri = p.ri;
+        d.qpad_intra = p.qpad_intra;
+        d.multi_intra = p.multi_intra;
+        d.kernel = p.kernel;
+        d.drain = false;
+    }
+    swplan::ScanPlan e = p;
+    e.set_drain(false);
+    for (const swplan::ScanPlan* q : {&d, &e})
+        CHECK(q->ri == p.ri && q->ri2 == p.ri2 && q->qpad_inter == p.qpad_inter && q->qpad_intra == p.qpad_intra &&
+                  q->qpad_intra2 == p.qpad_intra2 && q->npair == p.npair && q->ntri == p.ntri && q->nquad == p.nquad &&
+                  q->ntail == p.ntail && q->lpt == p.lpt && q->lpt_rows == p.lpt_rows && q->kernel == p.kernel &&
+                  q->intra_kernel == p.intra_kernel && q->multi_inter == p.multi_inter && !q->drain,
+              "%s: set_drain changed more than ri, qpad_intra and the name", name);
+    std::printf("%s: %s | %s ri %d ri2 %d\n", name, p.kernel.c_str(), p.intra_kernel.c_str(), p.ri, p.ri2);
+    return p;
+}
+
+// The forms below are what the scan driver chose before scan_plan existed
+// (read off that code, not off sw_plan.cpp).
+static void scan_forms(const sw_opts& o) {
+    const int kB62 = 11, kB50 = 15;  // the largest entries of BLOSUM62 and of the reference's BLOSUM50
+    // C2's 1/8 share shape: 1,065 blocks up to 891 columns, 3,122 long subjects
+    const Shape share8(1065, 891, 32, 3122, 7429, 891, o);
+    swplan::ScanPlan p = plan("share8-affine-q375", share8, 375, kB62, 12, 1);
+    CHECK(p.affine && p.x2_ok == 2 && p.lpt && p.ri2 == 6 && p.ntri > 0 && has(p.kernel, "+tri"), "share8 affine: %s", p.kernel.c_str());
+    CHECK(p.kernel.rfind("sw_inter_x2p<32,8,affine,fp16>", 0) == 0 && p.intra_kernel == "sw_intra_x2<6>", "share8 affine names");
+    p = plan("share8-linear-q375", share8, 375, kB50, 2, 2);
+    CHECK(!p.affine && p.lpt && p.lpt_rows == 96 && p.qpad_inter == 384 && p.ntri == 0, "share8 linear 375: %s", p.kernel.c_str());
+    CHECK(p.kernel.rfind("sw_inter_x2p<48,8,linear,fp16>", 0) == 0, "share8 linear 375: %s", p.kernel.c_str());
+    p = plan("share8-linear-q96", share8, 96, kB50, 2, 2);
+    CHECK(p.lpt && p.lpt_rows == 64 && p.qpad_inter == 128, "share8 linear 96: %s", p.kernel.c_str());
+    CHECK(p.kernel.rfind("sw_inter_x2p<32,8,linear,fp16>", 0) == 0, "share8 linear 96: %s", p.kernel.c_str());
+    p = plan("share8-linear-q97", share8, 97, kB50, 2, 2);
+    CHECK(p.lpt && p.lpt_rows == 96 && p.qpad_inter == 192, "share8 linear 97: %s", p.kernel.c_str());
+    // one pass of the two-strips kernel: no pair form, so no merged launch
+    for (int qlen : {1, 40, 64})
+        for (int lin = 0; lin < 2; ++lin) {
+            p = plan("share8-one-pass", share8, qlen, lin ? kB50 : kB62, lin ? 2 : 12, lin ? 2 : 1);
+            CHECK(!p.lpt && p.npair == 0 && p.ncoop == 0 && p.qpad_inter == 64, "one pass: qlen %d: %s", qlen, p.kernel.c_str());
+            CHECK(p.kernel == (lin ? "sw_inter_x2s<32,8,linear,fp16>" : "sw_inter_x2s<32,8,affine,fp16>"), "one pass: %s", p.kernel.c_str());
+        }
+    // a long query: the cost model wants 12 rows per lane; affine scans take
+    // the merged launch at 8 instead, unless it is off; linear ones keep 12
+    p = plan("share8-affine-q1400", share8, 1400, kB62, 12, 1);
+    CHECK(p.lpt && p.ri2 == 8 && p.qpad_intra2 == 1536, "affine 1400: ri2 %d %s", p.ri2, p.kernel.c_str());
+    {
+        sw_opts off = o;
+        off.lpt = 0;
+        const Shape s2(1065, 891, 32, 3122, 7429, 891, off);
+        p = plan("share8-affine-q1400-lpt0", s2, 1400, kB62, 12, 1);
+        CHECK(!p.lpt && p.ri2 == 12 && p.qpad_intra2 == 1536 && p.intra_kernel == "sw_intra_x2<12>", "affine 1400, lpt 0: ri2 %d", p.ri2);
+        CHECK(p.kernel == "sw_inter_x2p<32,8,affine,fp16>", "affine 1400, lpt 0: %s", p.kernel.c_str());
+        p = plan("share8-affine-q375-lpt0", s2, 375, kB62, 12, 1);
+        CHECK(!p.lpt && p.ri2 == 6 && p.kernel == "sw_inter_x2p<32,8,affine,fp16>", "affine 375, lpt 0: %s", p.kernel.c_str());
+    }
+    p = plan("share8-linear-q1400", share8, 1400, kB50, 2, 2);
+    CHECK(!p.lpt && p.ri2 == 12, "linear 1400: ri2 %d %s", p.ri2, p.kernel.c_str());
+    // the adaptive routes: a span of int16 blocks, int16 first over the long subjects
+    p = plan("share8-span5", share8, 375, kB50, 2, 2, false, 5);
+    CHECK(!p.lpt && p.nr == 5 && p.kernel == "sw_inter_x2p<32,8,linear,fp16>+int16[0,5)", "span 5: %s", p.kernel.c_str());
+    p = plan("share8-span5-one-pass", share8, 40, kB50, 2, 2, false, 5);
+    CHECK(!p.lpt && p.nr == 0 && p.kernel == "sw_inter_x2s<32,8,linear,fp16>", "span 5, one pass: %s", p.kernel.c_str());
+    p = plan("share8-i16-first", share8, 375, kB50, 2, 2, true, 0);
+    CHECK(!p.lpt && p.intra_i16_first && p.intra_kernel == "sw_intra_x2<6,int16>", "int16 first: %s", p.intra_kernel.c_str());
+    // beyond the static int16 bound: guarded; scales the fp16 cell cannot hold: int32 only
+    p = plan("share8-guarded", share8, 2000, kB62, 12, 1);
+    CHECK(p.x2_ok == 1 && p.shape.x2s && p.rescue, "guarded: x2_ok %d %s", p.x2_ok, p.kernel.c_str());
+    p = plan("share8-int32-affine", share8, 375, kB62, 120, 120);  // S + gap leaves the int8 profile too
+    CHECK(p.affine && p.x2_ok == 0 && !p.intra_x2 && !p.rescue && p.kernel == "sw_inter<32,8,affine>", "int32 affine: %s", p.kernel.c_str());
+    CHECK(p.intra_kernel.rfind("sw_intra<", 0) == 0 && has(p.intra_kernel, ",affine>"), "int32 affine: %s", p.intra_kernel.c_str());
+    p = plan("share8-int32-linear", share8, 375, kB62, 40, 40);
+    CHECK(!p.affine && p.x2_ok == 0 && p.kernel == "sw_inter<64,8,linear>" && has(p.intra_kernel, ",linear>"), "int32 linear: %s", p.kernel.c_str());
+    // 20 rows per lane: only without inter blocks (no merged launch could take the scan), affine gaps
+    const Shape only_long(0, 0, 0, 500, 4000, 64, o);
+    p = plan("only-long-affine-q1280", only_long, 1280, kB62, 12, 1);
+    CHECK(p.ri2 == 20 && p.intra_kernel == "sw_intra_x2<20>" && p.kernel.empty() && !p.lpt, "only long: ri2 %d", p.ri2);
+    p = plan("only-long-linear-q1280", only_long, 1280, kB50, 2, 2);
+    CHECK(p.ri2 != 20, "only long, linear: ri2 %d", p.ri2);
+    for (int qlen : {200, 1280, 2560, 5000})
+        for (int lin = 0; lin < 2; ++lin) {
+            p = plan("share8-never-20", share8, qlen, lin ? kB50 : kB62, lin ? 2 : 12, lin ? 2 : 1);
+            CHECK(p.ri2 != 20, "with blocks: qlen %d ri2 %d", qlen, p.ri2);
+        }
+    // no long subjects: no merged launch, whatever sw_opts lpt says
+    sw_opts on = o;
+    on.lpt = 1;
+    const Shape only_short(300, 700, 16, 0, 0, 700, on);
+    p = plan("only-short", only_short, 375, kB62, 12, 1);
+    CHECK(!p.lpt && p.npair > 0 && p.ri == 0 && p.intra_kernel == "none", "only short: %s", p.kernel.c_str());
 }
 
 int main() {
@@ -137,6 +309,7 @@ int main() {
     scenario("every-pair-pipelined", 300, 700, 48, 120, 3000, 150, 0, 0, false, false, 200, 64, 4, f);
     // no long subjects, no groups
     scenario("inter-only", 50, 300, 16, 0, 0, 0, 0, 0, true, false, 375, 64, 6, o);
+    scan_forms(o);
     if (failures) {
         std::printf("%d failures\n", failures);
         return 1;
