@@ -1388,6 +1388,7 @@ int inter_args(Scan& c) {
         a.f16_diff[1] = f16_pair(8 * ge);
         a.f16_diff[2] = f16_pair(16 * ge);
     }
+    a.re_last = p.re_last;  // the short last pass (x2s_pass)
     // its blocks: [blk_base, blk_first) by wave groups (the merged launch:
     // quads or tris first, the narrowest by tail pairs), one wave per block
     // from blk_first on; blocks below run beside it (coop, int16 pairs)
@@ -1477,6 +1478,10 @@ RescueStages rescue_stages(const Scan& c, const swk::IntraArgs& x, const BndRows
     s.a16.bnd_h = s.a32.bnd_h = r.h;
     s.a16.bnd_f = s.a32.bnd_f = r.f;
     s.a16.qpad = p.qpad_list;
+    // (the rescue stages keep full-height passes: the list kernel pads the
+    // query to its own pass height)
+    s.a16.re_last = p.affine ? 32 : 48;
+    s.a32.re_last = swplan::rescue_rows(p.affine);  // (the int32 kernels have one form)
     s.a16.rescue_list = items(c.listB);
     s.a16.rescue_count = c.listB;
     s.a16.rescue_max = nullptr;

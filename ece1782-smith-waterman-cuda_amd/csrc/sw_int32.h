@@ -326,7 +326,7 @@ __device__ __forceinline__ void intra_subject(const IntraArgs& a, int sid, uint8
     constexpr int RIP = intra_rip(RI);
     constexpr int S = intra_stride(RI);
     constexpr int CHUNK_BYTES = kProfileRows * kLanes * RIP;  // one chunk of the host profile
-    const int lane = threadIdx.x & (kLanes - 1);
+    const int lane = tid_x() & (kLanes - 1);
     const int L = a.subj_len[sid];
     const uint8_t* __restrict__ res = a.residues + a.subj_off[sid];
     int32_t* bnd_h = a.bnd_h + a.subj_off[sid];

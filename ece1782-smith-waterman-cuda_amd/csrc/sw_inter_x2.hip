@@ -202,9 +202,14 @@ __device__ __forceinline__ uint32_t to_f16_bits(uint32_t v16) {
 // the first row of each 16-row group S + bias + bias0: the diagonal entering
 // that row still carries the previous row group's bias, 16 ge above its own
 // (bias0 = -16 ge folds the shift back into the profile; see x2s_pass).
+// hi0: the hi image's first row below s0: R, or the strip height R - 4 of a
+// short pass (x2s_pass): 8-byte aligned only, so that image is loaded by
+// 8-byte halves.  (The short pass reads the first R - 4 rows of either image;
+// the rows after them are staged all the same, from inside the padded
+// profile: s0 + R - 4 + R < s0 + 2 R <= qpad.)
 template <int R, bool F16>
 __device__ __forceinline__ void stage_x2s(X2Lds<R>& L, const int16_t* __restrict__ prof, int stride, int s0,
-                                          int lane, int bias, int bias0, int img) {
+                                          int lane, int bias, int bias0, int img, int hi0 = R) {
     constexpr int RD = x2_row_dwords(R);
     constexpr int PER = kImgCodes * (R / 8);  // int4 loads per image
     constexpr uint32_t one = F16 ? 0x3c00u : 1u;
@@ -214,7 +219,14 @@ __device__ __forceinline__ void stage_x2s(X2Lds<R>& L, const int16_t* __restrict
         const int u = img < 0 ? t % PER : t;
         const int c = u / (R / 8);
         const int k = u % (R / 8);
-        const int4 v = *reinterpret_cast<const int4*>(prof + static_cast<size_t>(c) * stride + s0 + im * R + 8 * k);
+        const int16_t* src = prof + static_cast<size_t>(c) * stride + s0 + im * hi0 + 8 * k;
+        int4 v;
+        if (im && (hi0 & 7)) {
+            const int2 v0 = *reinterpret_cast<const int2*>(src), v1 = *reinterpret_cast<const int2*>(src + 4);
+            v = make_int4(v0.x, v0.y, v1.x, v1.y);
+        } else {
+            v = *reinterpret_cast<const int4*>(src);
+        }
         const uint32_t w[4] = {static_cast<uint32_t>(v.x), static_cast<uint32_t>(v.y), static_cast<uint32_t>(v.z),
                                static_cast<uint32_t>(v.w)};
         uint32_t o[8];
@@ -292,7 +304,9 @@ __device__ __forceinline__ h2 max3h(h2 a, h2 b, h2 c) {
     return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c);
 }
 
-template <int R, int SG, bool AFFINE, bool F16, int CR = 16>
+// SHORT: the block's last pass may take the short form (x2s_pass RL = R - 4);
+// the rescue stages, always full height, are built without it
+template <int R, int SG, bool AFFINE, bool F16, int CR = 16, bool SHORT = true>
 __device__ __forceinline__ bool x2s_block(const InterArgs& a, int blk, X2Lds<R>& L, int lane);
 
 // LIST: a rescue stage walking the device-side block list (a separate
@@ -307,7 +321,7 @@ __global__ __launch_bounds__(256, 2) void sw_inter_x2s(InterArgs a) {
     if constexpr (LIST) {
         const int n = __builtin_amdgcn_readfirstlane(*a.blk_count);
         for (int i = blockIdx.x * kWavesPerWG + wave; i < n; i += gridDim.x * kWavesPerWG)
-            x2s_block<R, SG, AFFINE, F16, CR>(a, list_take(a.blk_list, i), L, lane);
+            x2s_block<R, SG, AFFINE, F16, CR, false>(a, list_take(a.blk_list, i), L, lane);
         return;
     }
     const int blk = a.blk_first + blockIdx.x * kWavesPerWG + wave;
@@ -485,10 +499,10 @@ __device__ __forceinline__ void pair_wait(const int* prog, int wave, int need) {
 // restart; SG columns later the same for the hi image and the high halves.
 // The low strip's row -1 input of pass k's first columns was stored by pass
 // k-1's high strip at least one sub-group earlier (ncols >= 32).
-template <int R, int SG, bool AFFINE, bool F16, bool PAIR, int CR = 16, bool CHAIN = false>
+template <int R, int SG, bool AFFINE, bool F16, bool PAIR, int CR = 16, bool CHAIN = false, int RL = R>
 __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32_t ncols, uint64_t base, int lane,
                                          int s0, Best<F16>& best, const int4* ring_in, int4* ring_out,
-                                         int* tick, const PairSync* ps = nullptr) {
+                                         int* tick, const PairSync* ps = nullptr, int chain_passes = 1) {
     static_assert(!(CHAIN && PAIR), "chained passes: single-wave blocks only");
     // SG: sub-group width = the lag (columns) between the two strips
     // CR: profile rows per LDS chunk (16: 2 x 4 ds_read_b128 in flight; 8
@@ -515,7 +529,8 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
     const bool first = (s0 == 0);
     const bool last = (s0 + 2 * R >= a.qpad);
     // CHAIN: passes in this sweep and its virtual width
-    const uint32_t npass = CHAIN ? static_cast<uint32_t>((a.qpad + 2 * R - 1) / (2 * R)) : 1u;
+    const uint32_t npass = CHAIN ? static_cast<uint32_t>(chain_passes) : 1u;
+    const bool chain_last = CHAIN && static_cast<int>(npass) * 2 * R >= a.qpad;
     const uint32_t total = npass * ncols;
     const int sbias = F16 ? (AFFINE ? 2 : 1) * a.gap_extend : 0;
     // fp16: the images hold S + 2 ge (the diagonal comes from bias r - 1 + jj - 1;
@@ -526,7 +541,41 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
     const int gbias0 = F16 ? -kRowGroup * a.gap_extend : 0;
     // packed H of row -1 at the previous step, with the last row group's bias
     const uint32_t dtop0 = F16 ? a.f16_step[SG - 2 + kRowGroup] : 0u;
-    stage_x2s<R, F16>(L, prof16, a.prof_stride, s0, lane, sbias, gbias0, -1);
+    // The short pass (RL = R - 4; the callers take it for a query's last pass
+    // when a.re_last, swplan::short_rows, says so).  The query's rows end
+    // inside its last pass, and a packed op computes row r of both strips, so
+    // the short pass splits the rows evenly: low strip rows [s0, s0 + RL),
+    // high strip [s0 + RL, s0 + 2 RL); rows r >= RL of both strips are left out
+    // of the unrolled steps (straight-line code, as the full pass's: a form
+    // with one body and wave-uniform skips of 4-row quarters took any height
+    // but ran C2 4.6 % slower).
+    //  * The rows left out keep in H the start value of a strip, the floor
+    //    with the bias of column SG - 1, and every rebase takes SG ge off.
+    //    The fp16 maxima read H[RL] as the partner "cell (RL, jj - 1)" of row
+    //    RL - 1 (cell_d): from the first rebase on it lies below the floor of
+    //    the anti-diagonal it is compared on, which every real cell reaches,
+    //    so the maxima are unchanged; it only ever decreases, by finite
+    //    steps, so it is never NaN or +inf (far below the exact range it may
+    //    stop moving or, with a large ge over a long pass, reach -inf: it is
+    //    only compared, and max3 with -inf is the other two's maximum).
+    //  * The low strip's bottom row is row RL - 1, of bias (11 + jj) ge (RL =
+    //    28 or 44), while col_start and the hi image's first row take the
+    //    delay line at the last row group's bias, (15 + jj) ge for H and (16 +
+    //    jj) ge for F.  col_done adds 4 ge (a.f16_diff[0]) to both: the sums
+    //    are the values a row of bias 15 + jj holds for the same true H and F,
+    //    exact integers inside the documented range.
+    //  * The hi image starts at row s0 + RL: 8-byte aligned (stage_x2s).
+    //  * Never part of a chained sweep: x2s_block runs it after the chain,
+    //    so its first sub-group is a lag sub-group (the high strip idle).
+    constexpr bool kSh = RL < R;
+    // (its lane-dependent staging addresses are computed here, not hoisted
+    // out of the launch's entry loop, where they would be live across every form)
+    if constexpr (kSh) asm volatile("" : "+v"(lane));
+    static_assert(!kSh || (RL == R - 4 && !CHAIN), "rows per strip: R, or R - 4 outside a chain");
+    static_assert((R - 4 - 1) % kRowGroup == 11, "the short strip's bottom row: 4 ge under the last row's bias");
+    h2 dsh_h = {};
+    if constexpr (F16) dsh_h = __builtin_bit_cast(h2, a.f16_diff[0]);  // 4 ge
+    stage_x2s<R, F16>(L, prof16, a.prof_stride, s0, lane, sbias, gbias0, -1, RL);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -577,7 +626,7 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
     constexpr uint32_t RB = x2_row_dwords(R) * 4;
     const uint32_t blo = lds_addr(L.lo), bhi = lds_addr(L.hi);
     // LDS addresses of the code rows of the column being prefetched
-    uint32_t aa = code_row<RB>(rc, 0, blo), ab = code_row<RB>(rp, 0, bhi);
+    uint32_t aa = code_row<RB>(rc, 0, blo), ab = bhi + kPadCode * RB;  // (the pad code's row)
     read_x2a<CQ>(PL[0], PH[0], aa, ab, 0, 0);
 
     // sub-groups 0 .. total/SG: the last one runs the high strip only.
@@ -648,8 +697,10 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
             // what crosses the sub-group boundary (H as the next diagonal, E)
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                H[r] = H[r] - reb_h;
-                if constexpr (AFFINE) E[r] = E[r] - reb_h;
+                // (short form: of the rows left out only H[RL], the maxima's partner, is read)
+                if (r <= RL) H[r] = H[r] - reb_h;
+                if constexpr (AFFINE)
+                    if (r < RL) E[r] = E[r] - reb_h;
             }
             dtop = P::bits(P::from(dtop) - reb_h);
         }
@@ -723,8 +774,14 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
         };
         // end of column jj: its bottom row feeds the high strip SG steps later
         auto col_done = [&](const V up, const V f, const int jj) {
-            dl_h[jj] = P::bits(up);
-            if constexpr (AFFINE) dl_f[jj] = P::bits(f);
+            if constexpr (kSh && F16) {
+                // `up` and `f` are row RL - 1's: up to the last row group's bias
+                dl_h[jj] = P::bits(up + dsh_h);
+                if constexpr (AFFINE) dl_f[jj] = P::bits(f + dsh_h);
+            } else {
+                dl_h[jj] = P::bits(up);
+                if constexpr (AFFINE) dl_f[jj] = P::bits(f);
+            }
         };
         // row -1 inputs of column jj: low strip from HBM (previous pass),
         // high strip from the low strip's bottom row SG steps back (fp16:
@@ -762,23 +819,28 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
             if (k == 0) col_start(up, diag, f, jj);
             const int4(&pl)[CQ] = PL[t & 1];
             const int4(&ph)[CQ] = PH[t & 1];
+            // the chunk's rows below RL (n: a constant of the unrolled step)
+            const int n = RL - CR * k < CR ? (RL - CR * k > 0 ? RL - CR * k : 0) : CR;
             if constexpr (F16 && AFFINE) {
-                // the step's CR diagonal sums first (they read only the old H
+                // the step's diagonal sums first (they read only the old H
                 // values), so the dependent chain h -> m -> F of each row has
                 // independent work beside it
                 V dd[CR];
 #pragma unroll
                 for (int i = 0; i < CR; ++i)
-                    dd[i] = __builtin_elementwise_fma(P::from(word(pl, i)), P::from(word(ph, i)),
-                                                      i == 0 ? diag : H[CR * k + i - 1]);
+                    if (i < n)
+                        dd[i] = __builtin_elementwise_fma(P::from(word(pl, i)), P::from(word(ph, i)),
+                                                          i == 0 ? diag : H[CR * k + i - 1]);
 #pragma unroll
-                for (int i = 0; i < CR; ++i) asm volatile("" : "+v"(dd[i]));
+                for (int i = 0; i < CR; ++i)
+                    if (i < n) asm volatile("" : "+v"(dd[i]));
 #pragma unroll
-                for (int i = 0; i < CR; ++i) cell_d(CR * k + i, jj, up, diag, f, dd[i]);
+                for (int i = 0; i < CR; ++i)
+                    if (i < n) cell_d(CR * k + i, jj, up, diag, f, dd[i]);
             } else {
 #pragma unroll
                 for (int i = 0; i < CR; ++i)
-                    cell(CR * k + i, jj, up, diag, f, P::from(word(pl, i)), P::from(word(ph, i)));
+                    if (i < n) cell(CR * k + i, jj, up, diag, f, P::from(word(pl, i)), P::from(word(ph, i)));
             }
             if (k == NCH - 1) col_done(up, f, jj);
             // pin the running maxima at every step: left free, the compiler
@@ -790,7 +852,8 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
         // the high strip just finished columns [col0 - SG, col0)
         // the high strip's pass: the low strip's, or the one before while
         // the low strip is in its first sub-group
-        const bool high_last = CHAIN ? (lo_c == 0 ? lo_p : lo_p + 1) >= npass : last;
+        // (a chain that stops before the query's last pass stores its last boundary too)
+        const bool high_last = CHAIN ? chain_last && (lo_c == 0 ? lo_p : lo_p + 1) >= npass : last;
         if (!high_last && col0 >= SG) {
             // boundary out = the high halves of the delay line just written
             uint32_t hb[SG];
@@ -848,18 +911,34 @@ __device__ __forceinline__ uint32_t block_cols(const InterArgs& a, int blk) {
     return a.blk_cols ? a.blk_cols[blk] : a.blk_groups[blk] * kGroupCols;
 }
 
-template <int R, int SG, bool AFFINE, bool F16, int CR>
+template <int R, int SG, bool AFFINE, bool F16, int CR, bool SHORT>
 __device__ __forceinline__ bool x2s_block(const InterArgs& a, int blk, X2Lds<R>& L, int lane) {
     const uint32_t ncols = block_cols(a, blk);
     const uint64_t base = a.blk_off[blk] + static_cast<uint64_t>(lane) * kGroupCols;
     Best<F16> best;
     best.init(a);
     const uint64_t t0 = trace_now();
-    if (ncols >= 32 && a.qpad > 2 * R) {
-        x2s_pass<R, SG, AFFINE, F16, false, CR, true>(a, L, ncols, base, lane, 0, best, nullptr, nullptr, nullptr);
-    } else {
-        for (int s0 = 0; s0 < a.qpad && ncols > 0; s0 += 2 * R)
-            x2s_pass<R, SG, AFFINE, F16, false, CR>(a, L, ncols, base, lane, s0, best, nullptr, nullptr, nullptr);
+    // Blocks of 32 columns or more: the passes chained in one sweep.  A short
+    // last pass (a.re_last == R - 4: x2s_pass) runs on its own after the
+    // chain, one lag sub-group more per block for the rows left out: its
+    // ncols / 8 + 1 sub-groups at 7/8 of the rows against ncols / 8 chained
+    // ones pay from 56 columns on, so blocks of 32 .. 63 columns chain every
+    // pass at full height (narrower blocks never chain: short always pays).
+    const bool sh = SHORT && a.re_last == R - 4 && (ncols < 32 || ncols >= 64);
+    const int full_end = a.qpad - (sh ? 2 * R : 0);  // the full-height passes' rows
+    const int chained = ncols >= 32 ? full_end / (2 * R) : 0;
+    int s0 = 0;
+    if (chained > 1) {
+        x2s_pass<R, SG, AFFINE, F16, false, CR, true>(a, L, ncols, base, lane, 0, best, nullptr, nullptr, nullptr,
+                                                      nullptr, chained);
+        s0 = chained * 2 * R;
+    }
+    for (; s0 < full_end && ncols > 0; s0 += 2 * R)
+        x2s_pass<R, SG, AFFINE, F16, false, CR>(a, L, ncols, base, lane, s0, best, nullptr, nullptr, nullptr);
+    if constexpr (SHORT) {
+        if (sh && ncols > 0)
+            x2s_pass<R, SG, AFFINE, F16, false, CR, false, R - 4>(a, L, ncols, base, lane, full_end, best, nullptr,
+                                                                  nullptr, nullptr);
     }
     const bool flagged = x2s_finish<F16>(a, blk, lane, best.value(a));
     trace_block(a, blk, t0, lane, 0);
@@ -963,11 +1042,7 @@ __device__ __forceinline__ bool x2p_wg(const InterArgs& a, int wgi, int quad_end
     const int s0 = npair + nspare;
     const int twg = pwg + (tail - s0 + kWavesPerWG - 1) / kWavesPerWG;  // first tail-pair workgroup
     const bool tailp = MERGED && wgi >= twg;               // workgroup-uniform
-    if (MERGED && wgi >= pwg && !tailp) {
-        const int blk = s0 + (wgi - pwg) * kWavesPerWG + wave;
-        // workgroup-uniform branch: no barrier below is skipped by part of it
-        return blk < tail && x2s_block<R, SG, AFFINE, F16, kSingleCR>(a, blk, lds[wave], lane);
-    }
+    const bool singles = MERGED && wgi >= pwg && !tailp;   // workgroup-uniform: one block per wave
     const bool quad = !tailp && wgi < qwg;                 // workgroup-uniform
     const bool tri = tri_on && quad;                       // workgroup-uniform
     const bool spare = tri && wave == kWavesPerWG - 1;     // wave-uniform
@@ -993,17 +1068,24 @@ __device__ __forceinline__ bool x2p_wg(const InterArgs& a, int wgi, int quad_end
         __syncthreads();
     }
     bool flagged = false;
-    if (spare) {
-        const int sb = npair + wgi;  // (x2s_block synchronises with no other wave)
-        if (sb < s0) flagged = x2s_block<R, SG, AFFINE, F16, kSingleCR>(a, sb, lds[wave], lane);
-    } else if (blk < gend) {
+    // This wave's single-wave block, if it has one: a wave of a single-wave
+    // workgroup, or a tri workgroup's spare.  ONE x2s_block for both (each
+    // copy of it is three sub-group loops in every merged kernel); it
+    // synchronises with no other wave.
+    const int sb = singles ? s0 + (wgi - pwg) * kWavesPerWG + wave : npair + wgi;
+    if ((singles && sb < tail) || (spare && sb < s0))
+        flagged = x2s_block<R, SG, AFFINE, F16, kSingleCR>(a, sb, lds[wave], lane);
+    // workgroup-uniform: no barrier below is skipped by part of a workgroup
+    if (singles) return flagged;
+    if (!spare && blk < gend) {
         const uint32_t ncols = block_cols(a, blk);
         const uint64_t base = a.blk_off[blk] + static_cast<uint64_t>(lane) * kGroupCols;
         const int per = max(static_cast<int>(ncols) / SG + 1, G * kPairLag);
         const int4* rin = w > 0 ? ring[gi * (G - 1) + w - 1] : nullptr;
         int4* rout = w < G - 1 ? ring[gi * (G - 1) + w] : nullptr;
         PairSync ps{sm.prog, wave, 0, -1, 0, w < G - 1 ? wave + 1 : -1, static_cast<int>(ncols) / SG + 1};
-        for (int p = w; p < passes && ncols > 0; p += G) {
+        // pass p's place in the group's pipeline
+        auto enter = [&](const int p) {
             if constexpr (kPairFlags) {
                 // pass p's input: pass p - 1, by the wave before (this round)
                 // or by the group's last wave (the round before, in HBM)
@@ -1018,8 +1100,20 @@ __device__ __forceinline__ bool x2p_wg(const InterArgs& a, int wgi, int quad_end
                     ++tick;
                 }
             }
+        };
+        // the full-height passes of this wave, then the query's last pass in
+        // the short form where that is this wave's (a.re_last: x2s_pass)
+        const int pfull = passes - (a.re_last == R - 4 ? 1 : 0);
+        int p = w;
+        for (; p < pfull && ncols > 0; p += G) {
+            enter(p);
             x2s_pass<R, SG, AFFINE, F16, true, kPairCR>(a, lds[wave], ncols, base, lane, p * 2 * R, best, rin, rout,
                                                         &tick, &ps);
+        }
+        if (p == pfull && pfull < passes && ncols > 0) {
+            enter(p);
+            x2s_pass<R, SG, AFFINE, F16, true, kPairCR, false, R - 4>(a, lds[wave], ncols, base, lane, p * 2 * R, best,
+                                                                      rin, rout, &tick, &ps);
         }
     }
     (void)tmax;
@@ -1101,11 +1195,14 @@ constexpr size_t drain_smem() {
 template <bool AFFINE, int RI>
 __device__ __forceinline__ void lpt_drain(const DrainArgs* __restrict__ d, char* smem, int* task) {
     using D = DrainShape<AFFINE>;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
     for (;;) {
+        // (tid_x per task: what the stages derive from the lane is hoisted
+        // neither out of this loop nor out of the launch's entry loop)
+        const int tid = tid_x();
+        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        const int lane = tid & 63;
         __syncthreads();  // the LDS of the previous work is free, task may be rewritten
-        if (threadIdx.x == 0) {
+        if (tid == 0) {
             // list 1 first (whole-workgroup work, the longest), then A, 2, B
             constexpr int kOrder[4] = {2, 0, 3, 1};
             constexpr int kWant[4] = {2 * kWavesPerWG, kWavesPerWG, 1, kWavesPerWG};
@@ -1136,7 +1233,7 @@ __device__ __forceinline__ void lpt_drain(const DrainArgs* __restrict__ d, char*
                                                                reinterpret_cast<typename ix2::IntraImg<RI, false>::Elem*>(smem));
         } else if (kind == 1) {  // list A: int16 blocks, flagging into list B
             if (wave < n)
-                x2s_block<D::R16, D::SG16, AFFINE, false, 16>(d->a16, task[2 + wave],
+                x2s_block<D::R16, D::SG16, AFFINE, false, 16, false>(d->a16, task[2 + wave],
                                                               reinterpret_cast<X2Lds<D::R16>*>(smem)[wave], lane);
         } else if (kind == 4) {  // list 2: int32 subject (wave 0)
             if (wave == 0) intra_subject<RI, AFFINE, false>(d->i32, task[2], reinterpret_cast<uint8_t*>(smem));
@@ -1218,7 +1315,14 @@ __global__ __launch_bounds__(256, kGroupWavesPerEU) void sw_scan_lpt(LptParams p
         // Only a workgroup that appended an entry drains (and takes whatever is
         // listed, its own entries included): every entry is then taken by its
         // producer at the latest, and the rest of the grid pays one barrier.
-        const bool any = __syncthreads_or(flagged);
+        // (the workgroup's OR by hand, through task[2..5], free between the
+        // barriers around it: __syncthreads_or reads threadIdx.y and .z, which
+        // the compiler keeps live from kernel entry across every scan form)
+        const int tw = tid_x();
+        const bool wany = __builtin_amdgcn_ballot_w64(flagged) != 0;
+        if ((tw & 63) == 0) task[2 + (tw >> 6)] = wany;
+        __syncthreads();
+        const bool any = (task[2] | task[3] | task[4] | task[5]) != 0;
         // per-entry timeline (trace builds), after the per-block entries:
         // every wave of the workgroup is done here
         if (threadIdx.x == 0) trace_block(a, a.nblocks + k, t0, 0, item >= 0 ? 2 : 3);

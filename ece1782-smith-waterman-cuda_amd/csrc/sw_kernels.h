@@ -129,6 +129,9 @@ struct InterArgs {
     // SW_TRACE_FILE): [block][start, end, HW_ID, XCC_ID | kind << 32],
     // s_memrealtime (100 MHz) stamps, host-mapped memory
     uint64_t* trace;
+    // two-strips kernels (x2s_pass): rows per strip of the query's last pass
+    // (swplan::short_rows: the strip height R or R - 4; 0: every row)
+    int32_t re_last;
 };
 
 // Long subjects: one wave per subject, query rows spread over the 64 lanes,

@@ -410,6 +410,11 @@ int intra_x2_rows_for(int qlen, int longest, int wide, int forced) {
 // any other.
 bool lpt_supported(int ri) { return ri == 4 || ri == 6 || ri == 8; }
 
+int32_t short_rows(int32_t qlen, int pass_rows) {
+    const int32_t left = qlen - (round_up(qlen, pass_rows) / pass_rows - 1) * pass_rows;  // 1 .. pass_rows
+    return (left + 1) / 2 <= pass_rows / 2 - 4 ? pass_rows / 2 - 4 : pass_rows / 2;
+}
+
 // ---- the form of a scan ----------------------------------------------------
 PlanScoring plan_scoring(const int8_t* m, int go, int ge) {
     PlanScoring s;
@@ -507,6 +512,7 @@ ScanPlan scan_plan(const PlanDb& db, int32_t qlen, const PlanScoring& s, bool in
     // scans keep 64 rows (their E column would not fit).  sw_opts lpt_rows.
     p.lpt_rows = (p.lpt && !affine && O.lpt_rows != 64 && round_up(qlen, 96) > 96) ? 96 : 64;
     p.qpad_inter = round_up(qlen, p.lpt_rows == 96 ? 96 : R);
+    p.re_last = p.shape.x2s ? short_rows(qlen, p.lpt_rows == 96 ? 96 : R) : 0;
     if (p.lpt) {
         const int passes = p.qpad_inter / p.lpt_rows;
         // (tri_width takes precedence: where tris apply, quad_width is not consulted)

@@ -68,6 +68,11 @@ int intra_rows_for(int qlen, int longest);
 int intra_x2_rows_for(int qlen, int longest, int wide, int forced);
 // Rows per lane the merged launch is built for.
 bool lpt_supported(int ri);
+// Rows per strip (Re) of the last pass of a two-strips scan with passes of
+// pass_rows = 2 R query rows.  The kernels have two forms of a pass, R rows
+// per strip and R - 4 (sw_inter_x2.hip x2s_pass's RL): R - 4 when two strips
+// of that height hold the rows the query has left for its last pass, else R.
+int32_t short_rows(int32_t qlen, int pass_rows);
 
 // What a scan's form depends on of its scoring.
 struct PlanScoring {
@@ -99,6 +104,9 @@ struct ScanPlan {
     bool lpt = false;       // one merged launch (sw_scan_lpt)
     bool drain = false;     // ... that re-scores what it flags itself (set_drain)
     int lpt_rows = 64;      // its query rows per pass: 64, or 96 under linear gaps
+    // the two-strips kernels' short last pass: rows per strip (short_rows of
+    // the inter launch's pass height; 0: another kernel shape, every row runs)
+    int32_t re_last = 0;
     int32_t ntri = 0, nquad = 0, ntail = 0;  // its 3-wave groups, quads (= ntri when tris run), tail pairs
     bool multi_inter = false, multi_intra = false;  // more than one pass: boundary rows needed
     // what sw_last_kernel / sw_last_intra_kernel report; kernel is empty
