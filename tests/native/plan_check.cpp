@@ -6,7 +6,9 @@
 // single waves / tail pairs and pipelined pairs the policies choose, and the
 // table is sorted longest first.  And of the form of a scan (sw_plan.cpp
 // scan_plan): the conditions every plan meets, and the forms of the scans
-// whose routing is known.  Built and run by tests/test_plan.py.
+// whose routing is known, and one scoring on each side of every predicate
+// of the scoring (plan_scoring on real matrices).  Built and run by
+// tests/test_plan.py.
 #include <cstdio>
 #include <algorithm>
 #include <cstdlib>
@@ -288,6 +290,102 @@ static void scan_forms(const sw_opts& o) {
     CHECK(!p.lpt && p.npair > 0 && p.ri == 0 && p.intra_kernel == "none", "only short: %s", p.kernel.c_str());
 }
 
+// ---- the scoring predicates (sw_plan.cpp plan_scoring + scan_plan) ---------
+// A real 625-entry matrix: `off` everywhere, `diag` on the diagonal, and one
+// off-diagonal entry (row 3, column 17) holding the largest value `top`.
+struct Matrix {
+    int8_t m[625];
+    Matrix(int diag, int off, int top) {
+        for (int k = 0; k < 625; ++k) m[k] = static_cast<int8_t>(k / 25 == k % 25 ? diag : off);
+        m[3 * 25 + 17] = static_cast<int8_t>(top);
+    }
+};
+
+// plan()'s checks and line for a scan whose PlanScoring the library's own
+// plan_scoring filled from the matrix.
+static swplan::ScanPlan plan_real(const char* name, const Shape& sh, int qlen, const Matrix& mx, int go, int ge) {
+    const swplan::PlanScoring s = swplan::plan_scoring(mx.m, go, ge);
+    int top = 0;
+    for (int k = 0; k < 625; ++k) top = std::max<int>(top, mx.m[k]);
+    CHECK(s.max_s == top && s.go == go && s.ge == ge && s.biased_fits == (top + go <= 127),
+          "%s: plan_scoring max_s %d go %d ge %d biased_fits %d", name, s.max_s, s.go, s.ge, s.biased_fits);
+    return plan(name, sh, qlen, s.max_s, go, ge);
+}
+
+// One row on each side of each predicate of the scoring that switches kernel
+// families.  The database views: a few inter blocks beside a few long
+// subjects (tests/test_gpu_scoring_envelope.py scans one of that shape and
+// asserts the same names), and long subjects only.
+static void scoring_thresholds(const sw_opts& o) {
+    const Shape env(4, 1024, 40, 5, 1500, 1024, o);
+    const Shape env_long(0, 0, 0, 150, 1500, 64, o);
+    const Matrix m100(100, -50, 100), m11(4, -4, 11), m15(5, -5, 15), m0(-1, -3, 0);
+    swplan::ScanPlan p;
+    // biased_fits: S + gap = 127 is the int8 linear profile's last value
+    p = plan_real("env-int8-fits-27", env, 130, m100, 27, 27);
+    CHECK(!p.affine && p.f16 && p.kernel.rfind("sw_inter_x2p<48,8,linear,fp16>", 0) == 0, "int8-fits: %s", p.kernel.c_str());
+    p = plan_real("env-int8-over-28", env, 130, m100, 28, 28);
+    CHECK(p.affine && p.f16 && p.kernel.rfind("sw_inter_x2p<32,8,affine,fp16>", 0) == 0, "int8-over: %s", p.kernel.c_str());
+    {
+        const swplan::PlanScoring s = swplan::plan_scoring(m100.m, 28, 28);
+        CHECK(s.go == s.ge && !s.biased_fits, "int8-over: go %d ge %d biased_fits %d", s.go, s.ge, s.biased_fits);
+    }
+    // f16_fits: 2 max S + 27 ge + go at 1023 and 1024, by a large open, a large extend, a linear gap
+    const struct { const char* name; const Matrix* mx; int go, ge; bool fits; const char* i32; } rows[] = {
+        {"env-big-go-974-1", &m11, 974, 1, true, ""},    {"env-big-go-975-1", &m11, 975, 1, false, "sw_inter<32,8,affine>"},
+        {"env-big-ge-191-30", &m11, 191, 30, true, ""},  {"env-big-ge-192-30", &m11, 192, 30, false, "sw_inter<32,8,affine>"},
+        {"env-big-linear-35", &m15, 35, 35, true, ""},   {"env-big-linear-36", &m15, 36, 36, false, "sw_inter<64,8,linear>"},
+        {"env-non-positive-12-1", &m0, 12, 1, true, ""}, {"env-limits-1000-1000", &m100, 1000, 1000, false, "sw_inter<32,8,affine>"}};
+    for (const auto& r : rows) {
+        p = plan_real(r.name, env, 130, *r.mx, r.go, r.ge);
+        const int sum = 2 * swplan::plan_scoring(r.mx->m, r.go, r.ge).max_s + 27 * r.ge + r.go;
+        CHECK((sum < 1024) == r.fits, "%s: sum %d", r.name, sum);
+        CHECK(p.f16 == r.fits && p.intra_x2 == r.fits && (p.x2_ok != 0) == r.fits, "%s: f16 %d intra_x2 %d x2_ok %d", r.name,
+              p.f16, p.intra_x2, p.x2_ok);
+        if (r.fits)
+            CHECK(p.kernel.rfind(r.go == r.ge ? "sw_inter_x2p<48,8,linear,fp16>" : "sw_inter_x2p<32,8,affine,fp16>", 0) == 0 &&
+                      p.intra_kernel.rfind("sw_intra_x2<", 0) == 0, "%s: %s | %s", r.name, p.kernel.c_str(), p.intra_kernel.c_str());
+        else
+            CHECK(p.kernel == r.i32 && p.intra_kernel.rfind("sw_intra<", 0) == 0 && !p.rescue, "%s: %s | %s", r.name,
+                  p.kernel.c_str(), p.intra_kernel.c_str());
+    }
+    // the sums themselves: 1023 fits, 1024 does not
+    CHECK(2 * 11 + 27 * 1 + 974 == 1023 && 2 * 11 + 27 * 30 + 191 == 1023 && 2 * 15 + 28 * 35 == 1010 && 2 * 15 + 28 * 36 == 1038,
+          "the f16_fits rows are not at the bound");
+    // x2_ok 2 against 1: (qlen + 2) (max S + go) = 32,766 = 258 x 127 and 32,767 = 217 x 151;
+    // without the guard (sw_opts int16_guard 0) the second is an int32 scan
+    sw_opts ng = o;
+    ng.int16_guard = 0;
+    const Shape env_ng(4, 1024, 40, 5, 1500, 1024, ng);
+    p = plan_real("env-static-32766", env, 256, m11, 116, 1);
+    CHECK(p.x2_ok == 2 && p.f16, "32766: x2_ok %d", p.x2_ok);
+    p = plan_real("env-static-32766-guard0", env_ng, 256, m11, 116, 1);
+    CHECK(p.x2_ok == 2 && p.kernel.rfind("sw_inter_x2p<32,8,affine,fp16>", 0) == 0, "32766, guard 0: %s", p.kernel.c_str());
+    p = plan_real("env-static-32767", env, 215, m11, 140, 1);
+    CHECK(p.x2_ok == 1 && p.f16 && p.rescue, "32767: x2_ok %d", p.x2_ok);
+    p = plan_real("env-static-32767-guard0", env_ng, 215, m11, 140, 1);
+    CHECK(p.x2_ok == 1 && p.kernel == "sw_inter<32,8,affine>" && !p.rescue, "32767, guard 0: %s", p.kernel.c_str());
+    p = plan_real("env-static-32893", env, 257, m11, 116, 1);
+    CHECK(p.x2_ok == 1, "32893: x2_ok %d", p.x2_ok);
+    // ri2_wide (long subjects only): 2 max S + (intra_bias_rows(20) + 1) ge + go at 1023 and 1024
+    CHECK(swk::intra_bias_rows(swk::kIntraX2MaxRI) == 38 && 2 * 11 + 39 * 20 + 221 == 1023, "the ri2_wide rows are not at the bound");
+    p = plan_real("long-wide-221-20", env_long, 1280, m11, 221, 20);
+    CHECK(p.ri2 == 20 && p.intra_kernel == "sw_intra_x2<20>", "wide 221/20: %s", p.intra_kernel.c_str());
+    p = plan_real("long-wide-222-20", env_long, 1280, m11, 222, 20);
+    CHECK(p.ri2 != 20 && p.intra_x2 && p.intra_kernel.rfind("sw_intra_x2<", 0) == 0, "wide 222/20: %s", p.intra_kernel.c_str());
+    sw_opts f20 = o;
+    f20.intra_x2_rows = 20;  // forced: 20 rows only inside the bound
+    const Shape env_long20(0, 0, 0, 150, 1500, 64, f20);
+    p = plan_real("long-forced20-221-20", env_long20, 375, m11, 221, 20);
+    CHECK(p.ri2 == 20, "forced 20, 221/20: ri2 %d", p.ri2);
+    p = plan_real("long-forced20-222-20", env_long20, 375, m11, 222, 20);
+    CHECK(p.ri2 != 20 && p.ri2 > 0, "forced 20, 222/20: ri2 %d", p.ri2);
+    // ... and never beside inter blocks
+    const Shape env20(4, 1024, 40, 5, 1500, 1024, f20);
+    p = plan_real("env-forced20-12-1", env20, 375, m11, 12, 1);
+    CHECK(p.ri2 != 20 && p.ri2 > 0, "forced 20 with blocks: ri2 %d", p.ri2);
+}
+
 int main() {
     const sw_opts o = policy_defaults();
     // C2's 1/8 share shape: 1,065 blocks, 3,122 long subjects, 375-aa query
@@ -310,6 +408,7 @@ int main() {
     // no long subjects, no groups
     scenario("inter-only", 50, 300, 16, 0, 0, 0, 0, 0, true, false, 375, 64, 6, o);
     scan_forms(o);
+    scoring_thresholds(o);
     if (failures) {
         std::printf("%d failures\n", failures);
         return 1;

@@ -299,7 +299,7 @@ def test_long_query_int16_guard(sw, oracle, handle, knobs, variant, guard):
             assert k.startswith("sw_inter_x2s"), k
 
 
-def test_default_kernel_selection(sw, handle, knobs):
+def test_default_kernel_selection(sw, oracle, handle, knobs):
     """int16-safe scans run the packed two-strips-per-lane kernel; longer
     queries run it guarded; gaps too large for the guard band, or the guard
     switched off, run the int32 kernels."""
@@ -311,8 +311,9 @@ def test_default_kernel_selection(sw, handle, knobs):
     db.scan(q)
     assert family(handle) == "sw_inter_x2s<32,8,linear,fp16>"
     # beyond the static int16 bound but inside the guard band: guarded packed
-    db.scan(q, sw.capi.builtin_matrix(0), 100, 1)
+    got = db.scan(q, sw.capi.builtin_matrix(0), 100, 1)
     assert family(handle) == "sw_inter_x2s<32,8,affine,fp16>"
+    assert np.array_equal(got, oracle.scan(q, r, o, mat=sw.capi.builtin_matrix(0), gap_open=100, gap_extend=1))
     # max S + gap open >= 1000: int32
     db.scan(q, sw.capi.builtin_matrix(0), 1000, 1)
     assert handle.last_kernel() == "sw_inter<32,8,affine>"
@@ -589,8 +590,10 @@ def test_inter_widest_blocks_int16_first(sw, oracle, handle, knobs):
 
 @pytest.mark.parametrize("case", range(int(__import__("os").environ.get("SW_RANDOM_CASES", "24"))))
 def test_random_scoring_and_shapes(sw, oracle, handle, case):
-    """Seeded random cases against the oracle: a random symmetric matrix
-    (entries -9..13, positive diagonal), gap pairs with open >= extend and a
+    """Seeded random cases against the oracle: a random matrix (entries
+    -9..13, positive diagonal; symmetric on even cases, on odd ones the lower
+    triangle drawn afresh: row = query code, column = subject code), gap
+    pairs with open >= extend and a
     few with open < extend, ragged databases with subjects of 1..4,000
     residues, queries of 1..1,600, and the long threshold at the default, 64
     or 500, so every kernel family and both rescue chains get random inputs.
@@ -601,6 +604,9 @@ def test_random_scoring_and_shapes(sw, oracle, handle, case):
     m = rng.integers(-9, 14, size=(25, 25))
     m = np.triu(m) + np.triu(m, 1).T
     np.fill_diagonal(m, rng.integers(1, 14, size=25))
+    if case % 2:  # (a generator of its own: the case's other draws stay what they were)
+        m = np.triu(m) + np.tril(np.random.default_rng(5000 + case).integers(-9, 14, size=(25, 25)), -1)
+        assert (m != m.T).any()
     m = m.astype(np.int8).reshape(-1)
     ge = int(rng.integers(1, 8))
     go = int(ge + rng.integers(0, 15)) if case % 6 else int(rng.integers(1, ge + 1))

@@ -72,6 +72,9 @@ def test_traceback_matches_cpu_cpp(oracle):
 
 
 def test_python_restatement_agrees(oracle):
+    """The C oracle against score_linear_py (which indexes mat[q][s]): the
+    built-in matrices, and asymmetric ones with entries over the whole
+    -100..100 range the library accepts, gaps 1..60."""
     rng = np.random.default_rng(5)
     for mid in (0, 1, 2):
         mat = oracle.matrix(mid)
@@ -79,6 +82,73 @@ def test_python_restatement_agrees(oracle):
             q = rng.integers(0, 25, size=rng.integers(1, 40)).astype(np.uint8)
             s = rng.integers(0, 25, size=rng.integers(1, 40)).astype(np.uint8)
             assert oracle.score(q, s, mat) == oracle.score_linear_py(q, s, mat, 2)
+    for k in range(12):
+        mat = rng.integers(-100, 101, size=(25, 25)).astype(np.int8)
+        mat[rng.integers(0, 25), rng.integers(0, 25)] = 100     # both ends of the range occur
+        mat[rng.integers(0, 25), rng.integers(0, 25)] = -100
+        assert (mat != mat.T).any()
+        g = int(rng.integers(1, 61))
+        for _ in range(8):
+            q = rng.integers(0, 25, size=rng.integers(1, 40)).astype(np.uint8)
+            s = rng.integers(0, 25, size=rng.integers(1, 40)).astype(np.uint8)
+            want = oracle.score_linear_py(q, s, mat, g)
+            assert oracle.score(q, s, mat, g, g) == want
+            assert oracle.score(q, s, mat, g, g, force_affine=True) == want
+
+
+def one_entry_matrix():
+    """Only S[A][R] = 5 (row = query code A, column = subject code R), every
+    other entry -5."""
+    m = np.full((25, 25), -5, dtype=np.int8)
+    m[0, 1] = 5
+    return m
+
+
+def asym_matrix(rng):
+    """A random asymmetric matrix: entries -12..12, diagonal 3..13."""
+    m = rng.integers(-12, 13, size=(25, 25))
+    np.fill_diagonal(m, rng.integers(3, 14, size=25))
+    return m.astype(np.int8)
+
+
+def test_matrix_convention_row_is_query(oracle):
+    """The matrix's row is the query's code and its column the subject's
+    (include/sw_amd.h), in swo_score_*, swo_scan and both tracebacks: with
+    the one-entry matrix an all-A query scores 5 per residue of an all-R
+    subject, and nothing with the roles swapped."""
+    m = one_entry_matrix()
+    a, r = oracle.encode("AAAAAA"), oracle.encode("RRRR")
+    for go, ge in ((2, 2), (12, 1), (7, 3)):
+        assert oracle.score(a, r, m, go, ge) == 20
+        assert oracle.score(r, a, m, go, ge) == 0
+        assert oracle.score(a, r, m, go, go, force_affine=True) == 20
+        assert oracle.score(r, a, m, go, go, force_affine=True) == 0
+        offs = np.array([0, 4, 10], dtype=np.int64)
+        res = np.concatenate([r, a])
+        assert oracle.scan(a, res, offs, mat=m, gap_open=go, gap_extend=ge).tolist() == [20, 0]
+        assert oracle.scan(r, res, offs, mat=m, gap_open=go, gap_extend=ge).tolist() == [0, 0]
+        al = oracle.align(a, r, m, go, ge)
+        assert al["score"] == 20 and al["ops"] == "MMMM"
+        assert (al["q_end"] - al["q_begin"], al["s_begin"], al["s_end"]) == (3, 1, 4)
+        assert path_score(a, r, m, go, ge, al) == 20
+        assert oracle.align(r, a, m, go, ge)["score"] == 0
+
+
+@pytest.mark.parametrize("go,ge", [(2, 2), (12, 1), (7, 3)])
+def test_transposed_matrix_cannot_hide(oracle, go, ge):
+    """Under a random asymmetric matrix the scan's scores under m and m.T
+    differ on nearly every random subject (98-99 % of 300 when this was
+    written): a test that compares a kernel with the oracle under such a
+    matrix sees a transposed index."""
+    rng = np.random.default_rng(17)
+    m = asym_matrix(rng)
+    q = rng.integers(0, 25, size=130).astype(np.uint8)
+    lens = rng.integers(40, 300, size=300)
+    res = rng.integers(0, 25, size=int(lens.sum())).astype(np.uint8)
+    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    a = oracle.scan(q, res, offs, mat=m, gap_open=go, gap_extend=ge)
+    b = oracle.scan(q, res, offs, mat=m.T, gap_open=go, gap_extend=ge)
+    assert (a != b).mean() > 0.9, (a != b).mean()
 
 
 def test_affine_reduces_to_linear(oracle):
