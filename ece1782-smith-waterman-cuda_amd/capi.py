@@ -32,6 +32,8 @@ EXPORTED = (
     "sw_topk", "sw_topk_device", "sw_topk_keys_device", "sw_topk_device_ids", "sw_scan_topk",
     "sw_scan_rank_device", "sw_score_pair",
     "sw_align",
+    "sw_pssm_create", "sw_pssm_free", "sw_pssm_length", "sw_scan_pssm", "sw_scan_pssm_device",
+    "sw_scan_pssm_topk", "sw_align_pssm",
     "sw_db_save", "sw_db_load", "sw_db_subjects", "sw_db_create_synthetic", "sw_synth_tables",
     "sw_synth_lengths", "sw_group_create", "sw_group_destroy", "sw_group_info", "sw_group_handle",
     "sw_group_db_create", "sw_group_db_free", "sw_group_db_shard", "sw_group_scan", "sw_group_topk",
@@ -157,6 +159,14 @@ def lib():
         "sw_db_load": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.POINTER(vp)]),
         "sw_align": (ctypes.c_int, [vp, vp, u8p, i32, ctypes.POINTER(Scoring), i32p, i32,
                                     ctypes.POINTER(Alignment), ctypes.c_char_p, ctypes.c_int64]),
+        "sw_pssm_create": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int8), i32, ctypes.POINTER(vp)]),
+        "sw_pssm_free": (ctypes.c_int, [vp]),
+        "sw_pssm_length": (ctypes.c_int, [vp, i32p]),
+        "sw_scan_pssm": (ctypes.c_int, [vp, vp, vp, i32, i32, i32p]),
+        "sw_scan_pssm_device": (ctypes.c_int, [vp, vp, vp, i32, i32, vp]),
+        "sw_scan_pssm_topk": (ctypes.c_int, [vp, vp, vp, i32, i32, i32, i64p]),
+        "sw_align_pssm": (ctypes.c_int, [vp, vp, vp, i32, i32, i32p, i32,
+                                         ctypes.POINTER(Alignment), ctypes.c_char_p, ctypes.c_int64]),
         "sw_topk": (ctypes.c_int, [i32p, i64, i32, i32p, i32p]),
         "sw_topk_device": (ctypes.c_int, [vp, vp, i64, i64, i32, vp]),
         "sw_topk_keys_device": (ctypes.c_int, [vp, vp, i64, i32, vp]),
@@ -252,7 +262,7 @@ class Handle:
         _check(lib().sw_create(device, ctypes.byref(h)))
         self._h = h
         self.device = device
-        self._dbs = weakref.WeakSet()  # databases must be freed before the handle
+        self._dbs = weakref.WeakSet()  # databases (and PSSMs) must be freed before the handle
         if env_opts:
             _check(lib().sw_set_opts(h, ctypes.byref(opts_from_env())))
 
@@ -358,6 +368,47 @@ class Handle:
         out = ctypes.c_int32()
         _check(lib().sw_score_pair(self._h, qp, len(q), sp, len(s), sc.ptr(), ctypes.byref(out)))
         return out.value
+
+
+class Pssm:
+    """A device-resident position-specific scoring matrix (sw_pssm_create):
+    rows is [qlen][25] int8, rows[i][c] = score of subject code c at query
+    position i.  Takes the place of a query in Database.scan_pssm & co."""
+
+    def __init__(self, handle, rows):
+        self.handle = handle
+        r = np.asarray(rows)
+        if r.size and (r.ndim != 2 or r.shape[1] != SW_ALPHABET):
+            raise SWError("a PSSM is a [qlen][%d] table" % SW_ALPHABET)
+        if r.size and (r.min() < -128 or r.max() > 127):
+            raise SWError("sw_amd error -1: PSSM entries must be in -100..100")
+        r = np.ascontiguousarray(r, dtype=np.int8).reshape(-1, SW_ALPHABET)
+        p = ctypes.c_void_p()
+        _check(lib().sw_pssm_create(handle.ptr, r.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)), len(r),
+                                    ctypes.byref(p)))
+        self._p = p
+        handle._dbs.add(self)
+
+    @property
+    def ptr(self):
+        return self._p
+
+    def __len__(self):
+        n = ctypes.c_int32()
+        _check(lib().sw_pssm_length(self._p, ctypes.byref(n)))
+        return n.value
+
+    def close(self):
+        if self._p:
+            if self.handle.ptr:  # (a closed handle has closed us)
+                lib().sw_pssm_free(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Database:
@@ -511,6 +562,45 @@ class Database:
         buf = ctypes.create_string_buffer(max(n, 1) * stride)
         _check(lib().sw_align(self.handle.ptr, self._d, qp, len(q), sc.ptr(),
                               idv.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n, out, buf, stride))
+        res = []
+        for k in range(n):
+            a = out[k]
+            res.append({"score": a.score, "q_begin": a.q_begin, "q_end": a.q_end, "s_begin": a.s_begin,
+                        "s_end": a.s_end, "ops": buf.raw[k * stride: k * stride + a.ops_len].decode()})
+        return res
+
+    def scan_pssm(self, pssm, gap_open=2, gap_extend=None):
+        """Synchronous scan of a Pssm; int32 scores indexed by id (sw_scan_pssm)."""
+        out = np.zeros(self.n_out, dtype=np.int32)
+        _check(lib().sw_scan_pssm(self.handle.ptr, self._d, pssm.ptr, gap_open,
+                                  gap_open if gap_extend is None else gap_extend,
+                                  out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        return out
+
+    def scan_pssm_device(self, pssm, scores_dev_ptr, gap_open=2, gap_extend=None):
+        """Asynchronous PSSM scan on the handle's stream into a device int32 buffer."""
+        _check(lib().sw_scan_pssm_device(self.handle.ptr, self._d, pssm.ptr, gap_open,
+                                         gap_open if gap_extend is None else gap_extend,
+                                         ctypes.c_void_p(scores_dev_ptr)))
+
+    def scan_pssm_topk(self, pssm, k, gap_open=2, gap_extend=None):
+        """The k best subjects of a PSSM scan as int64 keys (as scan_topk)."""
+        out = np.zeros(k, dtype=np.int64)
+        _check(lib().sw_scan_pssm_topk(self.handle.ptr, self._d, pssm.ptr, gap_open,
+                                       gap_open if gap_extend is None else gap_extend, k,
+                                       out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return out
+
+    def align_pssm(self, pssm, ids, gap=2, gap_extend=None):
+        """Traceback of a Pssm against the subjects with these result ids
+        (sw_align_pssm; the tie rules and the result of align)."""
+        idv = np.ascontiguousarray(ids, dtype=np.int32)
+        n = len(idv)
+        out = (Alignment * max(n, 1))()
+        stride = len(pssm) + int(self.stats()["max_length"]) + 1
+        buf = ctypes.create_string_buffer(max(n, 1) * stride)
+        _check(lib().sw_align_pssm(self.handle.ptr, self._d, pssm.ptr, gap, gap if gap_extend is None else gap_extend,
+                                   idv.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n, out, buf, stride))
         res = []
         for k in range(n):
             a = out[k]

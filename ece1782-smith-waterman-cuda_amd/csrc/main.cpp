@@ -20,6 +20,12 @@
 // linear, G to the reference's 2).  --topk K prints only the K best subjects
 // (score descending, record id ascending), ranked on the device.  Without
 // these flags the output is the reference's, byte for byte.
+// Profile queries: --pssm FILE takes the place of --query (exactly one of the
+// two): a position-specific scoring matrix in the text format of
+// sw_solver_ext.h, scanned under --gap-open / --gap-extend (--matrix has no
+// meaning then and is an error).  The file and the flags are checked before
+// any GPU is touched.  Output: "Input profile: N positions", the id:score
+// lines, and the METRICS block with N as the query length.
 #include <sys/time.h>
 
 #include <algorithm>
@@ -47,7 +53,8 @@ double now_s() {
 void usage() {
     std::cout << "Smith-Waterman MI355X Usage:\n"
               << "  --help                Display this help message\n"
-              << "  --query arg           Path to query file (required)\n"
+              << "  --query arg           Path to query file (required, or --pssm)\n"
+              << "  --pssm arg            Path to a PSSM text file, in the place of --query\n"
               << "  --db arg              Path to database file (required; FASTA, or a .swdb file)\n"
               << "  --make-db arg         Write the FASTA --db as a binary .swdb database and exit\n"
               << "  --gpus arg            Shard the FASTA database over this many GPUs (default 1)\n"
@@ -87,7 +94,7 @@ int main(int argc, char* argv[]) {
             val = argv[++i];
         }
         if (key != "query" && key != "db" && key != "metrics-json" && key != "make-db" && key != "gpus" &&
-            key != "matrix" && key != "gap-open" && key != "gap-extend" && key != "topk") {
+            key != "matrix" && key != "gap-open" && key != "gap-extend" && key != "topk" && key != "pssm") {
             std::cerr << "unrecognised option '--" << key << "'\n";
             return 1;
         }
@@ -107,8 +114,18 @@ int main(int argc, char* argv[]) {
              << " padded residues." << endl;
         return 0;
     }
-    if (!opt.count("query") || !opt.count("db") || help || argc <= 1) {
+    const bool use_pssm = opt.count("pssm") != 0;
+    if (opt.count("query") + opt.count("pssm") != 1 || !opt.count("db") || help || argc <= 1) {
+        if (opt.count("query") && use_pssm) std::cerr << "--pssm takes the place of --query: give one of the two\n";
         usage();
+        return 1;
+    }
+    if (use_pssm && opt.count("matrix")) {
+        std::cerr << "--pssm carries its own scores: --matrix cannot be combined with it\n";
+        return 1;
+    }
+    if (use_pssm && opt.count("gpus") && std::atoi(opt["gpus"].c_str()) != 1) {
+        std::cerr << "--pssm scans on one GPU: --gpus cannot be combined with it\n";
         return 1;
     }
     if (opt.count("gpus")) {
@@ -122,7 +139,7 @@ int main(int argc, char* argv[]) {
     int gap_open = 2, gap_extend = 2, topk = 0;
     if (custom) {
         std::string err;
-        if (!sw_solver_read_matrix(opt.count("matrix") ? opt["matrix"] : "blosum50", mat, &err)) {
+        if (!use_pssm && !sw_solver_read_matrix(opt.count("matrix") ? opt["matrix"] : "blosum50", mat, &err)) {
             std::cerr << "--matrix " << err << "\n";
             return 1;
         }
@@ -135,7 +152,7 @@ int main(int argc, char* argv[]) {
             std::cerr << "--gap-extend must be an integer in 1..1000\n";
             return 1;
         }
-        sw_solver_set_scoring(mat, gap_open, gap_extend);
+        sw_solver_set_scoring(use_pssm ? nullptr : mat, gap_open, gap_extend);
     }
     if (opt.count("topk") && !parse_int(opt["topk"], 1, INT32_MAX, &topk)) {
         std::cerr << "--topk must be a positive integer\n";
@@ -144,11 +161,24 @@ int main(int argc, char* argv[]) {
     const std::string& dbpath = opt["db"];
     const bool binary = dbpath.size() > 5 && dbpath.compare(dbpath.size() - 5, 5, ".swdb") == 0;
 
-    FASTAQuery query(opt["query"], true);
-    cout << "Input buffer:";
-    query.print_buffer();
-    cout << endl;
-    string querySequence = query.get_buffer();
+    std::vector<int8_t> prows;  // --pssm: [positions][25]
+    if (use_pssm) {
+        std::string err;
+        if (!sw_solver_read_pssm(opt["pssm"], &prows, nullptr, &err)) {
+            std::cerr << "--pssm " << err << "\n";
+            return 1;
+        }
+    }
+    FASTAQuery query(use_pssm ? std::string() : opt["query"], true);  // (no file: an empty buffer)
+    if (use_pssm) {
+        cout << "Input profile: " << prows.size() / 25 << " positions" << endl;
+    } else {
+        cout << "Input buffer:";
+        query.print_buffer();
+        cout << endl;
+    }
+    // the query length of the METRICS block: the PSSM's positions
+    const string querySequence = use_pssm ? string(prows.size() / 25, 'X') : query.get_buffer();
 
     vector<seqid_score> result;
     result.reserve(600000);
@@ -160,7 +190,8 @@ int main(int argc, char* argv[]) {
         parse_s = now_s() - t_parse;
         const double t_solve = now_s();
         try {
-            if (topk) result = smith_waterman_cuda_topk(query, db, topk);
+            if (use_pssm) result = smith_waterman_cuda_pssm(prows, db, topk);
+            else if (topk) result = smith_waterman_cuda_topk(query, db, topk);
             else smith_waterman_cuda(query, db, result);
         } catch (const std::exception& e) {
             std::cerr << e.what() << "\n";
@@ -193,10 +224,14 @@ int main(int argc, char* argv[]) {
         sw_encode(q.data(), static_cast<int64_t>(q.size()), qc.data());
         // BLOSUM50 (SWSolver.cu:54-81), gap 2 (:7), unless chosen
         const sw_scoring sc = {custom ? mat : nullptr, gap_open, gap_extend};
+        sw_pssm* pssm = nullptr;
+        if (use_pssm && sw_pssm_create(h, prows.data(), static_cast<int32_t>(prows.size() / 25), &pssm))
+            return die("sw_pssm_create");
         const double t_solve = now_s();
         if (topk && topk <= 4096) {
             std::vector<int64_t> keys(static_cast<size_t>(topk));
-            if (sw_scan_topk(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, topk, keys.data()))
+            if (use_pssm ? sw_scan_pssm_topk(h, sdb, pssm, gap_open, gap_extend, topk, keys.data())
+                         : sw_scan_topk(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, topk, keys.data()))
                 return die("sw_scan_topk");
             for (int64_t key : keys) {
                 if (key == INT64_MIN) break;
@@ -205,7 +240,9 @@ int main(int argc, char* argv[]) {
             }
         } else {
             std::vector<int32_t> scores(static_cast<size_t>(st.max_id + 1), 0);
-            if (st.n_subjects && sw_scan(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, scores.data()))
+            if (st.n_subjects &&
+                (use_pssm ? sw_scan_pssm(h, sdb, pssm, gap_open, gap_extend, scores.data())
+                          : sw_scan(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, scores.data())))
                 return die("sw_scan");
             // the reference's report order: padded length descending, file
             // (= record id) order within a length (SWSolver.cu:309,384-390)
@@ -230,6 +267,7 @@ int main(int argc, char* argv[]) {
         // hold the subjects as written (older ones '/'-padded: the same sums)
         for (int64_t k = 0; k < st.n_subjects; ++k) length_sum += roundUp(static_cast<int>(lens[k]), TILE_SIZE);
         num_subjects = st.n_subjects;
+        sw_pssm_free(pssm);
         sw_db_free(sdb);
         sw_destroy(h);
     }

@@ -20,6 +20,12 @@
 //
 // Cost is O(|q| |s|) per hit — meant for the top hits of a scan, not the
 // database.
+//
+// Both sweeps are templates over a score functor for the diagonal term: a
+// residue sequence against the matrix (MatScore), or a position-specific
+// scoring matrix (PssmScore, sw_align_pssm), whose term is pssm[i-1][s[j-1]]
+// read from the resident table.  Tie rules, scratch layout and the walk back
+// are the same code.
 #include "sw_kernels.h"
 
 namespace swk {
@@ -88,22 +94,43 @@ __device__ void align_walk(const AlignArgs& a, const Best& bb, const uint8_t* T,
     r[5] = static_cast<int32_t>(n);
 }
 
+// The diagonal term's score S(query row i, subject code c), i 1-based: the two
+// forms of a query.  MatScore: a residue sequence against the 25 x 25 matrix
+// staged in LDS.  PssmScore: a position-specific table, read from the resident
+// transposed image (PssmProfileArgs) in global memory; no LDS table is staged.
+struct MatScore {
+    static constexpr bool kStaged = true;
+    const int8_t* smat;
+    const uint8_t* __restrict__ q;
+    __device__ MatScore(const AlignArgs& a, const int8_t* lds) : smat(lds), q(a.query) {}
+    __device__ __forceinline__ int operator()(int i, int c) const { return smat[25 * q[i - 1] + c]; }
+};
+struct PssmScore {
+    static constexpr bool kStaged = false;
+    const int8_t* __restrict__ t;
+    int ld;
+    __device__ PssmScore(const AlignArgs& a, const int8_t*) : t(a.pssm), ld(a.pssm_ld) {}
+    __device__ __forceinline__ int operator()(int i, int c) const { return t[static_cast<int64_t>(c) * ld + i - 1]; }
+};
+
+template <class Score>
 __global__ __launch_bounds__(kAlignThreads) void sw_align_linear(AlignArgs a) {
-    __shared__ int8_t smat[640];
+    __shared__ int8_t smat[Score::kStaged ? 640 : 16];
     __shared__ Best red[kAlignThreads];
     const int hit = blockIdx.x;
     const int tid = threadIdx.x;
     const int qlen = a.qlen;
     const int64_t soff = a.subj_off[hit];
     const int slen = static_cast<int>(a.subj_off[hit + 1] - soff);
-    const uint8_t* __restrict__ q = a.query;
     const uint8_t* __restrict__ s = a.subj + soff;
     const int W1 = qlen + 1;
     int32_t* Hb = a.hbuf + static_cast<int64_t>(hit) * 3 * W1;
     uint8_t* T = a.dirs + a.dirs_off[hit];
     const int gap = a.gap;
+    const Score score(a, smat);
 
-    for (int k = tid; k < 625; k += kAlignThreads) smat[k] = a.mat[k];
+    if constexpr (Score::kStaged)
+        for (int k = tid; k < 625; k += kAlignThreads) smat[k] = a.mat[k];
     for (int k = tid; k < 3 * W1; k += kAlignThreads) Hb[k] = 0;
     __syncthreads();
 
@@ -121,7 +148,7 @@ __global__ __launch_bounds__(kAlignThreads) void sw_align_linear(AlignArgs a) {
             if (left > h) { h = left; t = 1; }
             const int up = p1[i - 1] - gap;  // H(i-1, j)
             if (up > h) { h = up; t = 2; }
-            const int dg = p2[i - 1] + smat[25 * q[i - 1] + s[j - 1]];  // H(i-1, j-1) + S
+            const int dg = p2[i - 1] + score(i, s[j - 1]);  // H(i-1, j-1) + S
             if (dg > h) { h = dg; t = 3; }
             cur[i] = h;
             T[static_cast<int64_t>(d) * W1 + i] = static_cast<uint8_t>(t);
@@ -148,8 +175,9 @@ __global__ __launch_bounds__(kAlignThreads) void sw_align_linear(AlignArgs a) {
 // 0, the first strict maximum in row-major order ends the alignment.  The
 // sweep keeps three diagonals of H and two of E and F (7 x (qlen + 1) int32
 // per hit); E(i,j) reads diagonal d-1 at i, F(i,j) at i-1.
+template <class Score>
 __global__ __launch_bounds__(kAlignThreads) void sw_align_affine(AlignArgs a) {
-    __shared__ int8_t smat[640];
+    __shared__ int8_t smat[Score::kStaged ? 640 : 16];
     __shared__ Best red[kAlignThreads];
     constexpr int NEG = -(1 << 29);
     const int hit = blockIdx.x;
@@ -157,8 +185,8 @@ __global__ __launch_bounds__(kAlignThreads) void sw_align_affine(AlignArgs a) {
     const int qlen = a.qlen;
     const int64_t soff = a.subj_off[hit];
     const int slen = static_cast<int>(a.subj_off[hit + 1] - soff);
-    const uint8_t* __restrict__ q = a.query;
     const uint8_t* __restrict__ s = a.subj + soff;
+    const Score score(a, smat);
     const int W1 = qlen + 1;
     int32_t* Hb = a.hbuf + static_cast<int64_t>(hit) * 7 * W1;
     int32_t* Eb = Hb + 3 * W1;
@@ -166,7 +194,8 @@ __global__ __launch_bounds__(kAlignThreads) void sw_align_affine(AlignArgs a) {
     uint8_t* T = a.dirs + a.dirs_off[hit];
     const int go = a.gap, ge = a.gap_extend;
 
-    for (int k = tid; k < 625; k += kAlignThreads) smat[k] = a.mat[k];
+    if constexpr (Score::kStaged)
+        for (int k = tid; k < 625; k += kAlignThreads) smat[k] = a.mat[k];
     for (int k = tid; k < 3 * W1; k += kAlignThreads) Hb[k] = 0;
     for (int k = tid; k < 4 * W1; k += kAlignThreads) Eb[k] = NEG;  // E and F
     __syncthreads();
@@ -192,7 +221,7 @@ __global__ __launch_bounds__(kAlignThreads) void sw_align_affine(AlignArgs a) {
             int h = 0;
             if (e > h) { h = e; t = (t & 12) | 1; }
             if (f > h) { h = f; t = (t & 12) | 2; }
-            const int dg = p2[i - 1] + smat[25 * q[i - 1] + s[j - 1]];
+            const int dg = p2[i - 1] + score(i, s[j - 1]);
             if (dg > h) { h = dg; t = (t & 12) | 3; }
             cur[i] = h;
             ec[i] = e;
@@ -215,10 +244,18 @@ __global__ __launch_bounds__(kAlignThreads) void sw_align_affine(AlignArgs a) {
 
 hipError_t launch_align(const AlignArgs& a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
-    if (a.gap_extend != a.gap)
-        hipLaunchKernelGGL(sw_align_affine, dim3(a.n), dim3(kAlignThreads), 0, s, a);
-    else
-        hipLaunchKernelGGL(sw_align_linear, dim3(a.n), dim3(kAlignThreads), 0, s, a);
+    const bool affine = a.gap_extend != a.gap;
+    if (a.pssm) {
+        if (a.pssm_ld < a.qlen) return hipErrorInvalidValue;
+        if (affine)
+            hipLaunchKernelGGL(sw_align_affine<PssmScore>, dim3(a.n), dim3(kAlignThreads), 0, s, a);
+        else
+            hipLaunchKernelGGL(sw_align_linear<PssmScore>, dim3(a.n), dim3(kAlignThreads), 0, s, a);
+    } else if (affine) {
+        hipLaunchKernelGGL(sw_align_affine<MatScore>, dim3(a.n), dim3(kAlignThreads), 0, s, a);
+    } else {
+        hipLaunchKernelGGL(sw_align_linear<MatScore>, dim3(a.n), dim3(kAlignThreads), 0, s, a);
+    }
     return hipGetLastError();
 }
 

@@ -21,6 +21,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
+#include <new>
 #include <numeric>
 #include <string>
 #include <thread>
@@ -490,6 +492,19 @@ struct sw_db {
     int64_t id_base = 0;
 };
 
+// A position-specific scoring matrix resident on its handle's device
+// (sw_pssm_create): the transposed image swk::PssmProfileArgs describes,
+// uploaded once; the host keeps what planning and the adaptive state need.
+struct sw_pssm {
+    sw_handle* h = nullptr;
+    int32_t qlen = 0;
+    int32_t ld = 0;               // entries per code row of the image (>= qlen)
+    int8_t* d = nullptr;          // [25][ld]
+    std::vector<int8_t> image;    // the upload's source (alive while the copy may run)
+    int max_entry = 0;            // the largest entry (0 for an empty table)
+    uint64_t hash = 0;            // FNV-1a of the [qlen][25] table
+};
+
 namespace {
 
 // The planning policies' view of a database (sw_plan.h).
@@ -951,6 +966,11 @@ bool ensure_rbnd(sw_db* db, bool affine, bool intra_f) {
     return true;
 }
 
+int check_gaps(int go, int ge) {
+    if (go <= 0 || ge <= 0 || go > 1000 || ge > 1000) return fail(SW_E_INVALID, "gap penalties must be in 1..1000");
+    return SW_OK;
+}
+
 int check_scoring(const sw_scoring* sc, const int8_t** mat, int* go, int* ge) {
     *mat = kBlosum50Ref;
     *go = 2;
@@ -960,11 +980,43 @@ int check_scoring(const sw_scoring* sc, const int8_t** mat, int* go, int* ge) {
         *go = sc->gap_open;
         *ge = sc->gap_extend;
     }
-    if (*go <= 0 || *ge <= 0 || *go > 1000 || *ge > 1000)
-        return fail(SW_E_INVALID, "gap penalties must be in 1..1000");
+    if (int rc = check_gaps(*go, *ge)) return rc;
     for (int k = 0; k < 625; ++k)
         if ((*mat)[k] < -100 || (*mat)[k] > 100) return fail(SW_E_INVALID, "matrix entries must be in -100..100");
     return SW_OK;
+}
+
+// Where a scan's (or a traceback's) scores come from: residue codes against
+// a 25 x 25 matrix (sc), or a resident position-specific table with its gaps.
+// Only build_profiles / scan_profiles (and sw_align's upload) branch on it.
+struct QuerySrc {
+    const uint8_t* codes = nullptr;
+    const sw_scoring* sc = nullptr;
+    const sw_pssm* pssm = nullptr;
+    int go = 0, ge = 0;  // the PSSM form's gaps
+    int32_t qlen = 0;
+};
+QuerySrc seq_src(const uint8_t* q, int32_t qlen, const sw_scoring* sc) {
+    QuerySrc s;
+    s.codes = q;
+    s.qlen = qlen;
+    s.sc = sc;
+    return s;
+}
+QuerySrc pssm_src(const sw_pssm* p, int32_t go, int32_t ge) {
+    QuerySrc s;
+    s.pssm = p;
+    s.qlen = p ? p->qlen : 0;
+    s.go = go;
+    s.ge = ge;
+    return s;
+}
+// The PSSM entry points' own argument checks (the handle and the database are
+// the shared paths').
+int check_pssm(const sw_handle* h, const sw_pssm* p, int go, int ge) {
+    if (!h || !p) return fail(SW_E_INVALID, "null argument");
+    if (p->h->device != h->device) return fail(SW_E_INVALID, "the PSSM was created on another handle's device");
+    return check_gaps(go, ge);
 }
 
 // Query profiles.  Inter kernel: prof[c][i] = S[q_i][c] (+ gap for the
@@ -986,10 +1038,14 @@ struct Profiles {
 // Built on the device (swk::sw_build_profile, one launch per 2,048 query
 // rows; the first also zeroes the rescue lists' counters `reset`) in one of
 // the handle's profile slots, on the scan's stream.
-int build_profiles(sw_handle* h, const uint8_t* q, int32_t qlen, const int8_t* mat, int go, bool affine,
+// A PSSM's profiles come from its resident table (sw_build_profile_pssm): one
+// launch whatever the query length, nothing copied from the host.
+int build_profiles(sw_handle* h, const QuerySrc& src, const int8_t* mat, int go, bool affine,
                    int32_t qpad_inter, bool want16, int ri, int32_t qpad_intra, int32_t* const (&reset)[10],
                    Profiles* P) {
-    for (int32_t i = 0; i < qlen; ++i)
+    const uint8_t* q = src.codes;
+    const int32_t qlen = src.qlen;
+    for (int32_t i = 0; i < qlen && !src.pssm; ++i)
         if (q[i] >= SW_ALPHABET) return fail(SW_E_INVALID, "query residue code out of range (use sw_encode)");
     const int bias = affine ? 0 : go;
     P->stride = static_cast<int32_t>(round_up(std::max<int32_t>(qpad_inter, 16), 16));
@@ -1027,6 +1083,27 @@ int build_profiles(sw_handle* h, const uint8_t* q, int32_t qlen, const int8_t* m
     if (S.tail_pending) {  // a deferred tail still reads the slot's last profiles
         HIPCHECK(hipStreamWaitEvent(h->stream, S.tail_read, 0));
         S.tail_pending = false;
+    }
+    if (src.pssm) {
+        swk::PssmProfileArgs a{};
+        a.p8 = S.d + P->off8;
+        a.p16 = want16 ? reinterpret_cast<int16_t*>(S.d + P->off16) : nullptr;
+        a.pin = ri ? S.d + P->intra_off : nullptr;
+        a.stride = P->stride;
+        a.qlen = qlen;
+        a.bias = bias;
+        a.ri = ri;
+        a.rip = rip;
+        a.qpad_intra = ri ? qpad_intra : 0;
+        a.rows = std::max(P->stride, a.qpad_intra);
+        for (int k = 0; k < 10; ++k) a.reset[k] = reset[k];
+        a.pssm = src.pssm->d;
+        a.ld = src.pssm->ld;
+        HIPCHECK(swk::launch_build_profile_pssm(a, h->stream));
+        S.last_end = h->ev[3];
+        S.pending = true;
+        h->open_slot = P->slot;
+        return SW_OK;
     }
     swk::ProfileArgs a{};
     a.p8 = S.d + P->off8;
@@ -1322,7 +1399,7 @@ int scan_lists(Scan& c, bool defer) {
 // The profiles, and the rescue lists' counters (inter A, B, largest flagged
 // block; intra 1, 2; the drain's heads; the work counter) zeroed by the same
 // launch, before the fork so the side streams see them.
-int scan_profiles(Scan& c, const uint8_t* query, const int8_t* mat) {
+int scan_profiles(Scan& c, const QuerySrc& src, const int8_t* mat) {
     const swplan::ScanPlan& p = c.plan;
     const bool d = p.drain;
     int32_t* const cA = (p.rescue && c.db->nblocks) ? c.listA : nullptr;
@@ -1330,7 +1407,7 @@ int scan_profiles(Scan& c, const uint8_t* query, const int8_t* mat) {
     int32_t* const reset[10] = {cA, (cA && p.f16) ? c.listB : nullptr, (cA && p.f16) ? c.maxA : nullptr, c1,
                                 c1 ? c.list2 : nullptr, d ? c.headA : nullptr, d ? c.headA + 1 : nullptr,
                                 d ? c.head1 : nullptr, d ? c.head1 + 1 : nullptr, c.lpt_next};
-    const int rc = build_profiles(c.h, query, c.qlen, mat, c.sc.go, p.affine,
+    const int rc = build_profiles(c.h, src, mat, c.sc.go, p.affine,
                                   std::max({p.qpad_inter, p.qpad_rescue, p.qpad_coop, p.qpad_list, p.qpad_intra2}),
                                   p.shape.x2s || p.intra_x2, p.ri, p.qpad_intra, reset, &c.P);
     c.h->evpool[c.h->nscans - 1].merged = p.lpt;
@@ -1761,15 +1838,21 @@ int print_rescue_stats(const Scan& c) {
 // tail stream beside the next scan's fp16 passes (sw_handle::tail).
 // rq (nullable): rank the scan's scores too (a top-K launch after every
 // stage that writes them, before the scan's end event).
-int scan_impl_body(sw_handle* h, const sw_db* cdb, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
-                   int32_t* scores_dev, bool defer = false, const RankReq* rq = nullptr) {
+// src: the query source.  The two forms differ in the scoring's checks and
+// keys here and in scan_profiles; everything else is one path.
+int scan_impl_body(sw_handle* h, const sw_db* cdb, const QuerySrc& src, int32_t* scores_dev, bool defer = false,
+                   const RankReq* rq = nullptr) {
     sw_db* db = const_cast<sw_db*>(cdb);
-    if (!h || !db || (!query && qlen > 0) || qlen < 0 || !scores_dev) return fail(SW_E_INVALID, "null argument");
+    const uint8_t* query = src.codes;
+    const int32_t qlen = src.qlen;
+    if (!h || !db || (!src.pssm && !query && qlen > 0) || qlen < 0 || !scores_dev)
+        return fail(SW_E_INVALID, "null argument");
     if (rq) defer = false;  // the ranking reads every rescued score
-    const int8_t* mat;
-    int go, ge, rc;
+    const int8_t* mat = nullptr;
+    int go = src.go, ge = src.ge, rc;
+    if (src.pssm && (rc = check_pssm(h, src.pssm, go, ge))) return rc;
     if ((rc = check_fault(h))) return rc;
-    if ((rc = check_scoring(sc, &mat, &go, &ge))) return rc;
+    if (!src.pssm && (rc = check_scoring(src.sc, &mat, &go, &ge))) return rc;
     if (!db->built && (rc = build_db(db))) return rc;
     HIPCHECK(hipSetDevice(h->device));
     h->launches = 0;
@@ -1782,12 +1865,23 @@ int scan_impl_body(sw_handle* h, const sw_db* cdb, const uint8_t* query, int32_t
     c.db = db;
     c.qlen = qlen;
     c.scores = scores_dev;
-    c.sc = swplan::plan_scoring(mat, go, ge);
+    // The adaptive state's keys.  Bit 63 of skey is the form's tag: clear for
+    // a matrix scoring, set for a PSSM's (its gaps alone; the table is the
+    // "query", qhash), so a PSSM scan and a sequence scan of the same length
+    // never share an observation.
+    constexpr uint64_t kPssmTag = 1ull << 63;
     c.skey = 1469598103934665603ull;
-    for (int k = 0; k < 625; ++k) c.skey = (c.skey ^ static_cast<uint8_t>(mat[k])) * 1099511628211ull;
+    if (src.pssm) {
+        c.sc = swplan::plan_scoring_max(src.pssm->max_entry, go, ge);
+        c.qhash = src.pssm->hash;
+    } else {
+        c.sc = swplan::plan_scoring(mat, go, ge);
+        for (int k = 0; k < 625; ++k) c.skey = (c.skey ^ static_cast<uint8_t>(mat[k])) * 1099511628211ull;
+        c.qhash = 1469598103934665603ull;
+        for (int32_t k = 0; k < qlen; ++k) c.qhash = (c.qhash ^ query[k]) * 1099511628211ull;
+    }
     c.skey = ((c.skey ^ static_cast<uint32_t>(go)) * 1099511628211ull ^ static_cast<uint32_t>(ge)) * 1099511628211ull;
-    c.qhash = 1469598103934665603ull;
-    for (int32_t k = 0; k < qlen; ++k) c.qhash = (c.qhash ^ query[k]) * 1099511628211ull;
+    c.skey = src.pssm ? c.skey | kPssmTag : c.skey & ~kPssmTag;
 
     // The form of the scan: the two adaptive routes from the database's
     // earlier scans, then the plan; a merged launch drains its own rescue
@@ -1802,7 +1896,7 @@ int scan_impl_body(sw_handle* h, const sw_db* cdb, const uint8_t* query, int32_t
     db->last_pair_merged = p.npair != 0;
 
     if ((rc = scan_lists(c, defer))) return rc;
-    if ((rc = scan_profiles(c, query, mat))) return rc;
+    if ((rc = scan_profiles(c, src, mat))) return rc;
     if ((rc = scan_args(c))) return rc;
     if (!p.kernel.empty()) h->last_kernel = p.kernel;
     h->last_intra = p.intra_kernel;
@@ -1838,9 +1932,9 @@ int scan_impl_body(sw_handle* h, const sw_db* cdb, const uint8_t* query, int32_t
 // pending on an end event it never recorded: a later scan reusing the slot
 // would not wait for the kernels this one queued.  Drain the handle's streams
 // and release the slot instead.
-int scan_impl(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
-              int32_t* scores_dev, bool defer = false, const RankReq* rq = nullptr) {
-    const int rc = scan_impl_body(h, db, query, qlen, sc, scores_dev, defer, rq);
+int scan_impl(sw_handle* h, const sw_db* db, const QuerySrc& src, int32_t* scores_dev, bool defer = false,
+              const RankReq* rq = nullptr) {
+    const int rc = scan_impl_body(h, db, src, scores_dev, defer, rq);
     if (h && h->open_slot >= 0) {
         for (hipStream_t st : {h->stream, h->side, h->side2, h->tail})
             if (st) (void)hipStreamSynchronize(st);
@@ -1850,6 +1944,11 @@ int scan_impl(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen,
     return rc;
 }
 
+int scan_impl(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
+              int32_t* scores_dev, bool defer = false, const RankReq* rq = nullptr) {
+    return scan_impl(h, db, seq_src(query, qlen, sc), scores_dev, defer, rq);
+}
+
 int ensure_scores(sw_handle* h, size_t n) {
     if (n > h->scores_cap) {
         if (h->d_scores) HIPCHECK(hipFree(h->d_scores));
@@ -1857,6 +1956,44 @@ int ensure_scores(sw_handle* h, size_t n) {
         HIPCHECK(hipMalloc(reinterpret_cast<void**>(&h->d_scores), h->scores_cap * 4));
     }
     return SW_OK;
+}
+
+// sw_scan / sw_scan_pssm: the synchronous scan into host memory.
+int scan_host(sw_handle* h, const sw_db* db, const QuerySrc& src, int32_t* scores_host) {
+    if (!h || !db || !scores_host) return fail(SW_E_INVALID, "null argument");
+    const size_t n = static_cast<size_t>(db->max_id + 1);
+    if (n == 0) return SW_OK;
+    int rc;
+    HIPCHECK(hipSetDevice(h->device));
+    if ((rc = ensure_scores(h, n))) return rc;
+    // slots that no subject maps to read 0
+    HIPCHECK(hipMemsetAsync(h->d_scores, 0, n * 4, h->stream));
+    if ((rc = scan_impl(h, db, src, h->d_scores))) return rc;
+    HIPCHECK(hipMemcpyAsync(scores_host, h->d_scores, n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    return check_fault(h);
+}
+
+// sw_scan_topk / sw_scan_pssm_topk: a scan and its ranking, k keys copied back.
+int scan_topk_host(sw_handle* h, const sw_db* cdb, const QuerySrc& src, int32_t k, int64_t* keys_host) {
+    sw_db* db = const_cast<sw_db*>(cdb);
+    if (!h || !db || !keys_host || k <= 0 || k > 4096) return fail(SW_E_INVALID, "bad argument (1 <= k <= 4096)");
+    if (db->n == 0) {
+        for (int32_t i = 0; i < k; ++i) keys_host[i] = INT64_MIN;
+        return SW_OK;
+    }
+    int rc;
+    HIPCHECK(hipSetDevice(h->device));
+    const size_t slots = static_cast<size_t>(db->max_id + 1);
+    if ((rc = ensure_scores(h, slots + static_cast<size_t>(2 * k) + 2))) return rc;  // scores, then the k keys
+    int64_t* keys_dev = reinterpret_cast<int64_t*>(h->d_scores + round_up(static_cast<int64_t>(slots), 2));
+    // the ranking runs over the result ids of the subjects (rank_src)
+    const RankReq rq{k, nullptr, 0, keys_dev};
+    if ((rc = scan_impl(h, db, src, h->d_scores, false, &rq))) return rc;
+    HIPCHECK(hipMemcpyAsync(keys_host, keys_dev, static_cast<size_t>(k) * sizeof(int64_t), hipMemcpyDeviceToHost,
+                            h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    return check_fault(h);
 }
 
 }  // namespace
@@ -1884,7 +2021,7 @@ int topk_impl(sw_handle* h, const int32_t* scores, const int64_t* keys, int64_t 
 // ===========================================================================
 extern "C" {
 
-int32_t sw_version(void) { return 10000 * 0 + 100 * 1 + 0; }
+int32_t sw_version(void) { return 10000 * 0 + 100 * 2 + 0; }  // 0.2: sw_pssm_*
 
 #ifndef SW_SOURCE_ID
 #define SW_SOURCE_ID "unknown"
@@ -2352,18 +2489,76 @@ int sw_scan_device(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t 
 
 int sw_scan(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
             int32_t* scores_host) {
-    if (!h || !db || !scores_host) return fail(SW_E_INVALID, "null argument");
-    const size_t n = static_cast<size_t>(db->max_id + 1);
-    if (n == 0) return SW_OK;
-    int rc;
+    return scan_host(h, db, seq_src(query, qlen, sc), scores_host);
+}
+
+// ---- position-specific scoring matrices ----------------------------------
+int sw_pssm_create(sw_handle* h, const int8_t* rows, int32_t qlen, sw_pssm** out) {
+    if (!h || !out || qlen < 0 || (qlen > 0 && !rows)) return fail(SW_E_INVALID, "null argument");
+    *out = nullptr;
+    const int64_t n = static_cast<int64_t>(qlen) * SW_ALPHABET;
+    for (int64_t k = 0; k < n; ++k)
+        if (rows[k] < -100 || rows[k] > 100) return fail(SW_E_INVALID, "PSSM entries must be in -100..100");
+    std::unique_ptr<sw_pssm> p(new (std::nothrow) sw_pssm);
+    if (!p) return fail(SW_E_NOMEM, "out of host memory");
+    p->h = h;
+    p->qlen = qlen;
+    p->ld = static_cast<int32_t>(round_up(std::max<int32_t>(qlen, 1), 64));
+    p->hash = fnv1a(1469598103934665603ull, rows, static_cast<size_t>(n));
+    p->max_entry = n ? -128 : 0;
+    // the resident image: transposed, [code][ld] (swk::PssmProfileArgs)
+    p->image.assign(static_cast<size_t>(SW_ALPHABET) * p->ld, 0);
+    for (int32_t i = 0; i < qlen; ++i)
+        for (int c = 0; c < SW_ALPHABET; ++c) {
+            const int8_t v = rows[static_cast<int64_t>(i) * SW_ALPHABET + c];
+            p->max_entry = std::max<int>(p->max_entry, v);
+            p->image[static_cast<size_t>(c) * p->ld + i] = v;
+        }
     HIPCHECK(hipSetDevice(h->device));
-    if ((rc = ensure_scores(h, n))) return rc;
-    // slots that no subject maps to read 0
-    HIPCHECK(hipMemsetAsync(h->d_scores, 0, n * 4, h->stream));
-    if ((rc = scan_impl(h, db, query, qlen, sc, h->d_scores))) return rc;
-    HIPCHECK(hipMemcpyAsync(scores_host, h->d_scores, n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    return check_fault(h);
+    HIPCHECK(hipMalloc(reinterpret_cast<void**>(&p->d), p->image.size()));
+    const hipError_t e = hipMemcpyAsync(p->d, p->image.data(), p->image.size(), hipMemcpyHostToDevice, h->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(p->d);
+        return fail(SW_E_HIP, hipGetErrorString(e));
+    }
+    *out = p.release();
+    return SW_OK;
+}
+
+int sw_pssm_free(sw_pssm* p) {
+    if (!p) return SW_OK;
+    // scans in flight on the handle may still read the table
+    (void)hipSetDevice(p->h->device);
+    (void)hipStreamSynchronize(p->h->stream);
+    if (p->h->side) (void)hipStreamSynchronize(p->h->side);
+    if (p->h->tail) (void)hipStreamSynchronize(p->h->tail);
+    if (p->d) (void)hipFree(p->d);
+    delete p;
+    return SW_OK;
+}
+
+int sw_pssm_length(const sw_pssm* p, int32_t* qlen) {
+    if (!p || !qlen) return fail(SW_E_INVALID, "null argument");
+    *qlen = p->qlen;
+    return SW_OK;
+}
+
+int sw_scan_pssm(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open, int32_t gap_extend,
+                 int32_t* scores_host) {
+    if (int rc = check_pssm(h, p, gap_open, gap_extend)) return rc;
+    return scan_host(h, db, pssm_src(p, gap_open, gap_extend), scores_host);
+}
+
+int sw_scan_pssm_device(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open, int32_t gap_extend,
+                        int32_t* scores_dev) {
+    if (int rc = check_pssm(h, p, gap_open, gap_extend)) return rc;
+    return scan_impl(h, db, pssm_src(p, gap_open, gap_extend), scores_dev);
+}
+
+int sw_scan_pssm_topk(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open, int32_t gap_extend,
+                      int32_t k, int64_t* keys_host) {
+    if (int rc = check_pssm(h, p, gap_open, gap_extend)) return rc;
+    return scan_topk_host(h, db, pssm_src(p, gap_open, gap_extend), k, keys_host);
 }
 
 namespace {
@@ -2542,36 +2737,27 @@ int sw_scan_rank_device(sw_handle* h, const sw_db* cdb, const uint8_t* query, in
 
 int sw_scan_topk(sw_handle* h, const sw_db* cdb, const uint8_t* query, int32_t qlen, const sw_scoring* sc, int32_t k,
                  int64_t* keys_host) {
-    sw_db* db = const_cast<sw_db*>(cdb);
-    if (!h || !db || !keys_host || k <= 0 || k > 4096) return fail(SW_E_INVALID, "bad argument (1 <= k <= 4096)");
-    if (db->n == 0) {
-        for (int32_t i = 0; i < k; ++i) keys_host[i] = INT64_MIN;
-        return SW_OK;
-    }
-    int rc;
-    HIPCHECK(hipSetDevice(h->device));
-    const size_t slots = static_cast<size_t>(db->max_id + 1);
-    if ((rc = ensure_scores(h, slots + static_cast<size_t>(2 * k) + 2))) return rc;  // scores, then the k keys
-    int64_t* keys_dev = reinterpret_cast<int64_t*>(h->d_scores + round_up(static_cast<int64_t>(slots), 2));
-    // the ranking runs over the result ids of the subjects (rank_src)
-    const RankReq rq{k, nullptr, 0, keys_dev};
-    if ((rc = scan_impl(h, db, query, qlen, sc, h->d_scores, false, &rq))) return rc;
-    HIPCHECK(hipMemcpyAsync(keys_host, keys_dev, static_cast<size_t>(k) * sizeof(int64_t), hipMemcpyDeviceToHost,
-                            h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    return check_fault(h);
+    return scan_topk_host(h, cdb, seq_src(query, qlen, sc), k, keys_host);
 }
 
-int sw_align(sw_handle* h, const sw_db* cdb, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
-             const int32_t* ids, int32_t n, sw_alignment* out, char* ops, int64_t ops_stride) {
+}  // extern "C"
+
+namespace {
+// sw_align / sw_align_pssm: one traceback path; the forms differ in what is
+// uploaded (the codes and the matrix, or nothing: the table is resident) and
+// in the kernel's score functor (sw_align.hip).
+int align_impl(sw_handle* h, const sw_db* cdb, const QuerySrc& src, const int32_t* ids, int32_t n,
+               sw_alignment* out, char* ops, int64_t ops_stride) {
     sw_db* db = const_cast<sw_db*>(cdb);
-    if (!h || !db || n < 0 || qlen < 0 || (qlen > 0 && !query) || (n > 0 && (!ids || !out)) ||
+    const uint8_t* query = src.codes;
+    const int32_t qlen = src.qlen;
+    if (!h || !db || n < 0 || qlen < 0 || (!src.pssm && qlen > 0 && !query) || (n > 0 && (!ids || !out)) ||
         (ops && ops_stride <= 0))
         return fail(SW_E_INVALID, "null argument");
-    const int8_t* mat;
-    int go, ge, rc;
-    if ((rc = check_scoring(sc, &mat, &go, &ge))) return rc;
-    for (int32_t i = 0; i < qlen; ++i)
+    const int8_t* mat = nullptr;
+    int go = src.go, ge = src.ge, rc;
+    if (!src.pssm && (rc = check_scoring(src.sc, &mat, &go, &ge))) return rc;
+    for (int32_t i = 0; i < qlen && !src.pssm; ++i)
         if (query[i] >= SW_ALPHABET) return fail(SW_E_INVALID, "query residue code out of range (use sw_encode)");
     if (db->id_index.empty())
         for (int64_t k = 0; k < db->n; ++k) db->id_index.emplace(db->h_ids[k], k);
@@ -2623,21 +2809,21 @@ int sw_align(sw_handle* h, const sw_db* cdb, const uint8_t* query, int32_t qlen,
         auto alloc = [&](auto** p, size_t b) {
             if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(b, 1));
         };
-        alloc(&dq, qlen);
+        if (!src.pssm) alloc(&dq, qlen);
         alloc(&dsub, hsub.size());
         alloc(&doff, (m + 1) * sizeof(int64_t));
         alloc(&ddoff, m * sizeof(int64_t));
-        alloc(&dmat, 625);
+        if (!src.pssm) alloc(&dmat, 625);
         alloc(&ddir, static_cast<size_t>(dacc));
         // H: three diagonals; affine also two of E and two of F
         alloc(&dh, static_cast<size_t>(m) * (go != ge ? 7 : 3) * W1 * sizeof(int32_t));
         alloc(&dout, static_cast<size_t>(m) * 6 * sizeof(int32_t));
         if (ops) alloc(&dops, static_cast<size_t>(m) * ops_stride);
-        if (e == hipSuccess) e = hipMemcpyAsync(dq, query, qlen, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess && !src.pssm) e = hipMemcpyAsync(dq, query, qlen, hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(dsub, hsub.data(), hsub.size(), hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(doff, hoff.data(), (m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(ddoff, hdoff.data(), m * sizeof(int64_t), hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dmat, mat, 625, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess && !src.pssm) e = hipMemcpyAsync(dmat, mat, 625, hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess) {
             swk::AlignArgs a{};
             a.query = dq;
@@ -2646,6 +2832,8 @@ int sw_align(sw_handle* h, const sw_db* cdb, const uint8_t* query, int32_t qlen,
             a.subj_off = doff;
             a.n = m;
             a.mat = dmat;
+            a.pssm = src.pssm ? src.pssm->d : nullptr;
+            a.pssm_ld = src.pssm ? src.pssm->ld : 0;
             a.gap = go;
             a.gap_extend = ge;
             a.dirs = ddir;
@@ -2678,6 +2866,20 @@ int sw_align(sw_handle* h, const sw_db* cdb, const uint8_t* query, int32_t qlen,
         k0 = k1;
     }
     return SW_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sw_align(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
+             const int32_t* ids, int32_t n, sw_alignment* out, char* ops, int64_t ops_stride) {
+    return align_impl(h, db, seq_src(query, qlen, sc), ids, n, out, ops, ops_stride);
+}
+
+int sw_align_pssm(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open, int32_t gap_extend,
+                  const int32_t* ids, int32_t n, sw_alignment* out, char* ops, int64_t ops_stride) {
+    if (int rc = check_pssm(h, p, gap_open, gap_extend)) return rc;
+    return align_impl(h, db, pssm_src(p, gap_open, gap_extend), ids, n, out, ops, ops_stride);
 }
 
 int sw_score_pair(sw_handle* h, const uint8_t* query, int32_t qlen, const uint8_t* subject, int32_t slen,

@@ -365,6 +365,10 @@ struct AlignArgs {
     const int64_t* subj_off;   // n+1 offsets
     int32_t n;
     const int8_t* mat;         // 25 x 25
+    // the PSSM form (null: the matrix form; query and mat are then unused):
+    // the resident transposed table of PssmProfileArgs, pssm[c][pssm_ld]
+    const int8_t* pssm = nullptr;
+    int32_t pssm_ld = 0;
     int32_t gap;               // gap open (a 1-residue gap)
     int32_t gap_extend;        // each further residue (== gap: linear)
     uint8_t* dirs;             // per hit: (qlen + slen + 1) x (qlen + 1) direction bytes
@@ -421,6 +425,28 @@ struct ProfileArgs {
     uint8_t q[kProfQueryChunk];
 };
 hipError_t launch_build_profile(const ProfileArgs& a, hipStream_t s);
+// The same images from a position-specific scoring matrix (sw_pssm): the
+// scores cannot ride in the kernel arguments (25 bytes per query row), so the
+// table is resident in HBM and ONE launch covers rows [0, rows) of any query
+// length.  Resident layout: transposed, pssm[code c][ld] int8 in CODE order
+// (not stored order), entry [c][i] = score of subject code c at query row i,
+// ld >= qlen.  The builder's threads are consecutive rows of one code, so a
+// wave reads 64 consecutive bytes; the row-major [qlen][25] of the public
+// interface would put a wave's reads 25 bytes apart.
+struct PssmProfileArgs {
+    int8_t* p8;
+    int16_t* p16;
+    int8_t* pin;
+    int32_t stride;
+    int32_t qlen;
+    int32_t rows;  // rows built: max(stride, qpad_intra)
+    int32_t bias;
+    int32_t ri, rip, qpad_intra;
+    int32_t* reset[10];
+    const int8_t* pssm;
+    int32_t ld;
+};
+hipError_t launch_build_profile_pssm(const PssmProfileArgs& a, hipStream_t s);
 
 // A ranking input (sw_rank.h topk_key): entry g of [0, n) is keys[g], or the
 // key of (scores[r], gid ? gid[r] : id_base + r) with r = rid ? rid[g] : g —

@@ -428,6 +428,21 @@ PlanScoring plan_scoring(const int8_t* m, int go, int ge) {
     return s;
 }
 
+PlanScoring plan_scoring_max(int max_entry, int go, int ge) {
+    PlanScoring s;
+    s.go = go;
+    s.ge = ge;
+    s.max_s = std::max(0, max_entry);
+    s.biased_fits = max_entry + go <= 127;
+    return s;
+}
+
+PlanScoring plan_scoring_pssm(const int8_t* rows, int32_t qlen, int go, int ge) {
+    int mx = -128;
+    for (int64_t k = 0; k < static_cast<int64_t>(qlen) * 25; ++k) mx = std::max<int>(mx, rows[k]);
+    return plan_scoring_max(mx, go, ge);
+}
+
 ScanPlan scan_plan(const PlanDb& db, int32_t qlen, const PlanScoring& s, bool intra_i16_first, int32_t i16_span) {
     const sw_opts& O = *db.opts;
     const int max_s = s.max_s, go = s.go, ge = s.ge;

@@ -81,6 +81,12 @@ struct PlanScoring {
     bool biased_fits = true;  // matrix + gap fits the linear kernels' int8 profile
 };
 PlanScoring plan_scoring(const int8_t* matrix625, int go, int ge);
+// The same for a position-specific scoring matrix (sw_pssm): rows is
+// [qlen][25] int8; max_s and biased_fits follow the table's entries, so a
+// table that contains a matrix's largest entry plans as that matrix.
+PlanScoring plan_scoring_pssm(const int8_t* rows, int32_t qlen, int go, int ge);
+// ... and from the largest entry alone (what sw_pssm_create records).
+PlanScoring plan_scoring_max(int max_entry, int go, int ge);
 
 // The form of one scan (qlen > 0): everything sw_capi.cpp's enqueue stages
 // read.  Final when scan_plan returns, but for set_drain.

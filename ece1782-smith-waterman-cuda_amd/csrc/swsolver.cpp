@@ -301,6 +301,174 @@ bool sw_solver_read_matrix(const std::string& spec, int8_t out[625], std::string
     return true;
 }
 
+// The PSSM text format (sw_solver_ext.h; pssm.py restates this parser).
+bool sw_solver_read_pssm(const std::string& path, std::vector<int8_t>* rows, std::string* consensus,
+                         std::string* err) {
+    auto bad = [&](const std::string& why) {
+        if (err) *err = path + ": " + why;
+        return false;
+    };
+    std::ifstream in(path.c_str());
+    if (!in) return bad("cannot open PSSM file");
+    static const char kLetters[] = "ARNDCQEGHILKMFPSTWYVBJZX*";  // code order (SWSolver.cu:17-41)
+    auto is_letter = [](const std::string& t) {
+        return t.size() == 1 && (std::isalpha(static_cast<unsigned char>(t[0])) || t[0] == '*');
+    };
+    auto code_of = [&](const std::string& t) -> int {
+        const char* p = std::strchr(kLetters, std::toupper(static_cast<unsigned char>(t[0])));
+        return p && *p ? static_cast<int>(p - kLetters) : -1;
+    };
+    auto is_int = [](const std::string& t) {
+        size_t k = (t[0] == '+' || t[0] == '-') ? 1 : 0;
+        if (k == t.size()) return false;
+        for (; k < t.size(); ++k)
+            if (!std::isdigit(static_cast<unsigned char>(t[k]))) return false;
+        return true;
+    };
+    std::vector<int> col;  // the code of each named column
+    bool named[25] = {};
+    bool header = false;
+    if (rows) rows->clear();
+    if (consensus) consensus->clear();
+    size_t nrows = 0;
+    std::string line;
+    while (std::getline(in, line)) {
+        std::istringstream ls(line);
+        std::vector<std::string> tok;
+        for (std::string t; ls >> t;) tok.push_back(t);
+        if (tok.empty() || tok[0][0] == '#') continue;
+        if (!header) {
+            bool all = true;
+            for (const std::string& t : tok) all = all && is_letter(t);
+            if (!all) continue;  // lines before the header
+            for (const std::string& t : tok) {
+                const int c = code_of(t);
+                if (c < 0) return bad("unknown residue letter '" + t + "' in the header");
+                if (named[c]) break;  // NCBI repeats the letters for its percentage columns
+                named[c] = true;
+                col.push_back(c);
+            }
+            header = true;
+            continue;
+        }
+        // a row: [position] [consensus letter] scores...; without a letter a
+        // leading position is recognised by the row holding more tokens than columns
+        size_t at = 0;
+        bool pos = false;
+        int cons = -1;
+        if (tok.size() >= 2 && is_int(tok[0]) && is_letter(tok[1])) {
+            pos = true;
+            at = 1;
+        }
+        if (at < tok.size() && is_letter(tok[at])) {
+            cons = code_of(tok[at]);
+            if (cons < 0) return bad("unknown residue letter '" + tok[at] + "'");
+            ++at;
+        } else if (is_int(tok[0]) && tok.size() > col.size()) {
+            pos = true;
+            at = 1;
+        }
+        if (at >= tok.size()) {
+            if (pos) return bad("short row '" + line + "'");
+            break;
+        }
+        if (!is_int(tok[at])) break;  // not a row: the table has ended
+        if (tok.size() - at < col.size())
+            return bad("short row " + std::to_string(nrows + 1) + ": " + std::to_string(tok.size() - at) + " of " +
+                       std::to_string(col.size()) + " entries");
+        int v[25];
+        int lo = 101;
+        for (size_t j = 0; j < col.size(); ++j) {
+            const std::string& t = tok[at + j];
+            if (!is_int(t)) return bad("bad entry '" + t + "' in row " + std::to_string(nrows + 1));
+            const long x = t.size() > 5 ? 1000 : std::strtol(t.c_str(), nullptr, 10);
+            if (x < -100 || x > 100) return bad("entry '" + t + "' outside -100..100 in row " + std::to_string(nrows + 1));
+            v[col[j]] = static_cast<int>(x);
+            lo = std::min(lo, v[col[j]]);
+        }
+        // unnamed columns: B, Z, J from their pairs, the rest from X or the row's minimum
+        bool have[25];
+        std::memcpy(have, named, sizeof have);
+        static const int kPair[3][3] = {{20, 2, 3}, {22, 5, 6}, {21, 9, 10}};  // B: N D, Z: Q E, J: I L
+        for (const auto& p : kPair)
+            if (!named[p[0]] && named[p[1]] && named[p[2]]) {
+                const int s = v[p[1]] + v[p[2]];
+                v[p[0]] = s >= 0 ? s / 2 : -((-s + 1) / 2);  // floor
+                have[p[0]] = true;
+            }
+        for (int c = 0; c < 25; ++c)
+            if (!have[c]) v[c] = named[23] ? v[23] : lo;
+        if (cons < 0) {  // no consensus given: the best-scoring named column (first in code order)
+            for (int c = 0; c < 25; ++c)
+                if (named[c] && (cons < 0 || v[c] > v[cons])) cons = c;
+        }
+        if (rows)
+            for (int c = 0; c < 25; ++c) rows->push_back(static_cast<int8_t>(v[c]));
+        if (consensus) consensus->push_back(kLetters[cons]);
+        ++nrows;
+    }
+    if (!header) return bad("no header line of residue letters");
+    if (nrows == 0) return bad("no rows after the header");
+    return true;
+}
+
+std::vector<seqid_score> smith_waterman_cuda_pssm(const std::vector<int8_t>& rows, FASTADatabase& db, int k) {
+    if (k < 0) throw std::invalid_argument("top-k needs k >= 0");
+    if (rows.size() % 25 != 0) throw std::invalid_argument("a PSSM holds 25 entries per row");
+    std::lock_guard<std::mutex> lock(g_mu);
+    const Flat f = timed_flatten(db, true);  // the subjects as written, as under any set scoring
+    const int64_t n = static_cast<int64_t>(f.record_ids.size());
+    const int32_t qlen = static_cast<int32_t>(rows.size() / 25);
+    std::vector<seqid_score> out;
+    g_timing.gpus = 1;
+    double t0 = now_s();
+    sw_handle* h = handle();
+    g_timing.init_s = now_s() - t0;
+    t0 = now_s();
+    bool ids_ok = n > 0;
+    for (int id : f.record_ids) ids_ok = ids_ok && id >= 0;
+    const bool device_topk = k > 0 && k <= 4096 && ids_ok;
+    std::vector<int32_t> ids(f.record_ids.begin(), f.record_ids.end());
+    sw_db* sdb = nullptr;
+    sw_pssm* p = nullptr;
+    check(sw_db_create(h, f.residues.data(), f.offsets.data(), n, device_topk ? ids.data() : nullptr, &sdb),
+          "sw_db_create");
+    int rc = sw_pssm_create(h, rows.data(), qlen, &p);
+    g_timing.upload_s = now_s() - t0;
+    t0 = now_s();
+    std::vector<int64_t> keys(static_cast<size_t>(device_topk ? k : 0));
+    std::vector<int32_t> scores(static_cast<size_t>(device_topk ? 0 : n), 0);
+    const char* what = "sw_pssm_create";
+    if (rc == SW_OK && device_topk) {
+        what = "sw_scan_pssm_topk";
+        rc = sw_scan_pssm_topk(h, sdb, p, g_sc.go, g_sc.ge, k, keys.data());
+    } else if (rc == SW_OK && n > 0) {
+        what = "sw_scan_pssm";
+        rc = sw_scan_pssm(h, sdb, p, g_sc.go, g_sc.ge, scores.data());
+    }
+    g_timing.scan_s = now_s() - t0;
+    sw_pssm_free(p);
+    sw_db_free(sdb);
+    check(rc, what);
+    if (device_topk) {
+        for (int64_t key : keys) {
+            if (key == INT64_MIN) break;  // fewer subjects than k
+            out.push_back(std::make_pair(static_cast<int>((int64_t{1} << 31) - 1 - (key & 0xffffffff)),
+                                         static_cast<int>(key >> 32)));
+        }
+        return out;
+    }
+    for (int64_t i = 0; i < n; ++i) out.push_back(std::make_pair(f.record_ids[i], scores[i]));
+    if (k > 0) {  // beyond the device top-K's k (or a headerless file's id -1): ranked here
+        const size_t kk = std::min<size_t>(out.size(), static_cast<size_t>(k));
+        std::partial_sort(out.begin(), out.begin() + kk, out.end(), [](const seqid_score& a, const seqid_score& b) {
+            return a.second != b.second ? a.second > b.second : a.first < b.first;
+        });
+        out.resize(kk);
+    }
+    return out;
+}
+
 void sw_solver_set_scoring(const int8_t* matrix625, int gap_open, int gap_extend) {
     if (gap_open < 1 || gap_open > 1000 || gap_extend < 1 || gap_extend > 1000)
         throw std::invalid_argument("gap penalties must be in 1..1000");

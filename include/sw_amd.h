@@ -391,6 +391,42 @@ SW_API int sw_align(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t
                     const sw_scoring* sc, const int32_t* ids, int32_t n, sw_alignment* out,
                     char* ops, int64_t ops_stride);
 
+/* ---- profile (PSSM) queries ------------------------------------------------
+ * A position-specific scoring matrix in the place of a query: a [qlen][25]
+ * int8 table, rows[i*25 + c] = score of subject residue code c at query
+ * position i (a PSI-BLAST checkpoint, a family profile; the reference scores
+ * residues against one 25 x 25 table only, SWSolver.cu:54-81).  Every scan
+ * kernel reads a per-query profile already; a PSSM only changes what that
+ * profile is built from, so every kernel family, the guard bands, the ranking
+ * and the traceback serve it unchanged, and the table derived from a sequence
+ * and a matrix (rows[i] = matrix[q[i]]) scans bit for bit as sw_scan does.
+ *   sw_pssm_create : validates the entries (-100..100) and qlen >= 0, uploads
+ *                    the table once, asynchronously on the handle's stream
+ *                    (rows may be freed on return); qlen == 0 is valid and
+ *                    scans to all zeros, as the empty query does.
+ *   sw_pssm_free   : waits for the handle's stream (scans in flight read the
+ *                    table); the handle must outlive the PSSM.
+ *   sw_scan_pssm, sw_scan_pssm_device, sw_scan_pssm_topk, sw_align_pssm :
+ *                    as sw_scan, sw_scan_device, sw_scan_topk and sw_align,
+ *                    with the gap model given as two integers (1..1000;
+ *                    equal = linear).  A PSSM scan copies nothing from the
+ *                    host.  A PSSM of another handle's device is SW_E_INVALID.
+ * Out of scope: batches of PSSMs, the sw_group_* forms, sw_score_pair,
+ * position-specific gap costs, and building a PSSM from hits.              */
+typedef struct sw_pssm sw_pssm;
+SW_API int sw_pssm_create(sw_handle* h, const int8_t* rows, int32_t qlen, sw_pssm** out);
+SW_API int sw_pssm_free(sw_pssm* p);
+SW_API int sw_pssm_length(const sw_pssm* p, int32_t* qlen);
+SW_API int sw_scan_pssm(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open,
+                        int32_t gap_extend, int32_t* scores_host);
+SW_API int sw_scan_pssm_device(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open,
+                               int32_t gap_extend, int32_t* scores_dev);
+SW_API int sw_scan_pssm_topk(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open,
+                             int32_t gap_extend, int32_t k, int64_t* keys_host);
+SW_API int sw_align_pssm(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open,
+                         int32_t gap_extend, const int32_t* ids, int32_t n, sw_alignment* out,
+                         char* ops, int64_t ops_stride);
+
 /* ---- single pair ---------------------------------------------------------
  * One query against one subject on the GPU (wavefront kernel); the GPU
  * analogue of the cpu.cpp pair program's score (cpu.cpp:43-74).         */

@@ -65,4 +65,35 @@ bool sw_solver_read_matrix(const std::string& spec, int8_t out[625], std::string
  * the database is smaller.  k > 4096 ranks every score on the host. */
 std::vector<seqid_score> smith_waterman_cuda_topk(FASTAQuery& query, FASTADatabase& db, int k);
 
+/* Profile (PSSM) queries (sw_amd.h sw_pssm_*; `main --pssm FILE`).
+ * sw_solver_read_pssm reads a text PSSM into rows ([positions][25] int8 in
+ * code order) and its consensus (one letter per position):
+ *   - blank lines and lines starting with '#' are ignored, and so is every
+ *     line before the header;
+ *   - the header is the first line whose tokens are all single residue
+ *     letters; its columns are the leading run of distinct letters, stopping
+ *     at the first repeat (an NCBI ASCII PSSM repeats its 20 letters for the
+ *     percentage columns);
+ *   - each following line is one position: an optional integer position, an
+ *     optional residue letter (the consensus; without one, the best-scoring
+ *     named column), then at least one integer per column; further tokens are
+ *     ignored.  Without a letter, a leading position is recognised by the line
+ *     holding more tokens than the header has columns;
+ *   - the first line that is not such a row ends the table;
+ *   - columns the header does not name: B, Z and J take floor((a + b) / 2) of
+ *     their pair (N/D, Q/E, I/L) when both are named; every other one takes
+ *     the X column when X is named, else the row's minimum.
+ * False and *err on a bad file: "no header", "unknown residue letter",
+ * "short row", "bad entry", "-100..100", "no rows".
+ * smith_waterman_cuda_pssm scans the database with the table in the query's
+ * place, under the gaps of sw_solver_set_scoring (default 2/2), subjects as
+ * written; k = 0: every subject in the reference's report order, k > 0: the
+ * k best (score descending, record id ascending).  One GPU.
+ * Out of scope: batches of PSSMs, several GPUs (sw_group_*), sw_score_pair,
+ * position-specific gap costs, building a PSSM from hits. */
+bool sw_solver_read_pssm(const std::string& path, std::vector<int8_t>* rows, std::string* consensus,
+                         std::string* err);
+std::vector<seqid_score> smith_waterman_cuda_pssm(const std::vector<int8_t>& rows, FASTADatabase& db,
+                                                  int k /* 0 = all, in the reference's report order */);
+
 #endif /* SW_SOLVER_EXT_H */
