@@ -13,8 +13,6 @@
 //       -> one asynchronous launch per kernel on the handle's stream;
 //   * read managed scores back in packing order (:383-390)
 //       -> kernels write scores[id] directly.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
 #include <atomic>
@@ -29,9 +27,13 @@
 #include <unordered_map>
 #include <vector>
 
-#include "sw_amd.h"
-#include "sw_kernels.h"
+#include "sw_host.h"
 #include "sw_plan.h"
+
+using swk::DevPtr;
+using swk::Event;
+using swk::HostPtr;
+using swk::Stream;
 
 namespace {
 
@@ -56,16 +58,8 @@ int fail(int code, const std::string& msg) {
 // record event k of the current scan's set on stream s
 #define MARK(k, s)                                  \
     do {                                            \
-        HIPCHECK(hipEventRecord(h->ev[k], (s)));    \
+        HIPCHECK(hipEventRecord(h->ev[k].get(), (s)));    \
         *h->ev_rec |= 1u << (k);                    \
-    } while (0)
-
-
-#define HIPCHECK(expr)                                                                  \
-    do {                                                                                \
-        hipError_t e_ = (expr);                                                         \
-        if (e_ != hipSuccess)                                                           \
-            return fail(SW_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
     } while (0)
 
 // ---- built-in matrices (code order ARNDCQEGHILKMFPSTWYVBJZX*) ------------
@@ -217,7 +211,7 @@ struct ScanEvents {
     // 0 fork, 1 intra done (side), 2 inter done (main), 3 end, and around
     // each inter kernel on its own stream: 4/5 the cooperative kernel
     // (side2), 6/7 the per-wave kernel (main)
-    hipEvent_t ev[8] = {};
+    Event ev[8];
     unsigned rec = 0;  // bit k: ev[k] was recorded by this scan (read_events
                        // falls back for the others: each record is a packet
                        // the command processor spends microseconds on)
@@ -242,32 +236,33 @@ sw_opts default_opts() {
 struct sw_handle {
     int device = 0;
     int cus = 0;  // compute units of the device
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    Stream stream;  // the handle's own, or the caller's (sw_set_stream): borrowed, given up
+    bool own_stream = false;  // ... before the owner would destroy it
+    ~sw_handle() { if (!own_stream) stream.release(); }
     // One event set per scan since the last sw_timing_reset (grows as needed,
     // reused after a reset), so a caller can time many back-to-back scans
     // without synchronising between them.
     std::vector<ScanEvents> evpool;
     size_t nscans = 0;
-    hipEvent_t* ev = nullptr;  // event set of the current scan
+    Event* ev = nullptr;  // event set of the current scan (an alias into evpool, as ev_rec)
     unsigned* ev_rec = nullptr;
     // The intra kernel runs on a side stream, concurrently with the inter
     // kernel (fork/join through ev[0] and ev[1]).
-    hipStream_t side = nullptr;
-    hipStream_t side2 = nullptr;  // the cooperative wide-block kernel
+    Stream side;
+    Stream side2;  // the cooperative wide-block kernel
     // Deferred rescue tails (the queries of a batch but the last): a scan's
     // re-scoring stages (int16 / int32 list kernels) run on `tail` after its
     // fp16 passes, while the next query's fp16 passes start on the main and
     // side streams.  Lists and boundary rows of the tail are its own
     // (parity-indexed lists, sw_db::d_rbnd_*), so nothing is shared with the
     // passes running beside it.
-    hipStream_t tail = nullptr;
-    hipEvent_t main_done = nullptr, side_done = nullptr;  // fp16 passes of the scan being deferred
-    hipEvent_t tail_done[2] = {};                         // per list parity
+    Stream tail;
+    Event main_done, side_done;  // fp16 passes of the scan being deferred
+    Event tail_done[2];  // per list parity
     bool tail_pending[2] = {};
     int parity = 0;                                       // list set of the next scan
-    hipEvent_t coop_done = nullptr;
-    hipEvent_t fork2 = nullptr;  // side2 starts after the rescue counters are reset
+    Event coop_done;
+    Event fork2;  // side2 starts after the rescue counters are reset
     // per-query workspace: profiles (inter: [32][stride]; intra: lane-slotted
     // chunks) built on the device by the scan's first launch.  A ring of
     // slots: a deferred rescue tail (batches) may still read the profiles of
@@ -278,29 +273,29 @@ struct sw_handle {
     // scan_impl) then see scans a few queries back instead of none at all
     // when many scans are enqueued at once.
     struct ProfSlot {
-        int8_t* d = nullptr;
+        DevPtr<int8_t> d;
         size_t dcap = 0;
         // the end event (ev[3]) of the slot's last scan: reusing the slot
         // waits for it.  Not an event of its own: each event record is a
         // packet the command processor spends ~5 us on between two kernels
         // (rocprofv3 trace of C2's 1/8 share, scripts/step_gaps.py)
-        hipEvent_t last_end = nullptr;
+        hipEvent_t last_end = nullptr;  // (an alias into evpool)
         bool pending = false;
-        hipEvent_t tail_read = nullptr;  // a deferred rescue tail has read the slot
+        Event tail_read;  // a deferred rescue tail has read the slot
         bool tail_pending = false;
     };
     // pinned staging of database uploads (build_db): the host packs one
     // buffer while the other's copy runs
-    uint8_t* stage[2] = {};
+    HostPtr<uint8_t> stage[2];
     size_t stage_cap = 0;
-    hipEvent_t stage_ev[2] = {};
+    Event stage_ev[2];
     bool stage_pending[2] = {};
     static constexpr int kProfSlots = 4;
     ProfSlot prof[kProfSlots];
     int prof_next = 0;
-    int32_t* d_scores = nullptr;  // for the synchronous sw_scan
+    DevPtr<int32_t> d_scores;  // for the synchronous sw_scan
     size_t scores_cap = 0;
-    int64_t* d_topk_work = nullptr;  // device top-K workspace
+    DevPtr<int64_t> d_topk_work;  // device top-K workspace
     std::string last_kernel = "none";  // per-wave inter kernel of the last scan
     std::string last_intra = "none";   // long-subject kernel of the last scan
     size_t topk_cap = 0;
@@ -310,8 +305,8 @@ struct sw_handle {
     // host-mapped fault word (swk::DrainArgs::fault): set by a kernel that
     // had to skip work it could not do (list_wait_take's timeout); the next
     // call on the handle fails with SW_E_DEVICE instead of returning scores
-    int32_t* h_fault = nullptr;
-    int32_t* d_fault = nullptr;
+    HostPtr<int32_t> h_fault;
+    int32_t* d_fault = nullptr;  // the device address of h_fault (an alias)
     int open_slot = -1;  // profile slot pending on an ev[3] this scan has not recorded yet
     sw_opts opts = default_opts();  // kernel-form overrides (sw_set_opts); all -1 = the library's choice
 };
@@ -325,13 +320,25 @@ static std::atomic<uint64_t> g_fault_epoch{0};
 // A kernel of this handle reported a fault since the last check (sw_kernels.h
 // list_wait_take): fail loudly, once.
 static int check_fault(sw_handle* h) {
-    if (h && h->h_fault && __atomic_load_n(h->h_fault, __ATOMIC_ACQUIRE)) {
-        __atomic_store_n(h->h_fault, 0, __ATOMIC_RELEASE);
+    if (h && h->h_fault.get() && __atomic_load_n(h->h_fault.get(), __ATOMIC_ACQUIRE)) {
+        __atomic_store_n(h->h_fault.get(), 0, __ATOMIC_RELEASE);
         g_fault_epoch.fetch_add(1);
         return fail(SW_E_DEVICE, "sw_scan_lpt: a claimed rescue-list entry never appeared; the handle's scans "
                                  "since the last successful call may hold unrescued scores");
     }
     return SW_OK;
+}
+
+// Wait for everything queued on the handle's streams (before a release, or
+// after a failed scan); the first error, for the callers that check.
+static hipError_t quiesce(sw_handle* h) {
+    hipError_t first = hipSuccess;
+    for (hipStream_t st : {h->stream.get(), h->side.get(), h->side2.get(), h->tail.get()})
+        if (st) {
+            const hipError_t e = hipStreamSynchronize(st);
+            if (first == hipSuccess) first = e;
+        }
+    return first;
 }
 
 // What a scan's fp16 pass flagged, read back without waiting: one or two
@@ -345,8 +352,8 @@ struct Readback {
         int32_t qlen = 0, nr = 0;
         bool operator==(const Obs& o) const { return key == o.key && qhash == o.qhash && qlen == o.qlen && nr == o.nr; }
     };
-    int32_t* host = nullptr;  // pinned [2]
-    hipEvent_t ev = nullptr;
+    HostPtr<int32_t> host;  // pinned [2]
+    Event ev;               // both or neither (readback_record)
     bool pending = false;
     bool seen = false;  // `last` holds an observation
     Obs sent, last;     // of the pending readback; of the last one taken
@@ -357,13 +364,17 @@ namespace {
 // readback is pending or o is the last one taken.
 int readback_record(Readback& r, const Readback::Obs& o, const int32_t* w0, const int32_t* w1, hipStream_t s) {
     if (r.pending || (r.seen && r.last == o)) return SW_OK;
-    if (!r.host) {
-        HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&r.host), 2 * sizeof(int32_t), hipHostMallocDefault));
-        HIPCHECK(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
+    if (!r.host.get()) {
+        HostPtr<int32_t> host;
+        Event ev;
+        HIPCHECK(swk::host_alloc(host, 2 * sizeof(int32_t), hipHostMallocDefault));
+        HIPCHECK(swk::event_create(ev, hipEventDisableTiming));
+        r.host = std::move(host);
+        r.ev = std::move(ev);
     }
-    HIPCHECK(hipMemcpyAsync(r.host, w0, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (w1) HIPCHECK(hipMemcpyAsync(r.host + 1, w1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipEventRecord(r.ev, s));
+    HIPCHECK(hipMemcpyAsync(r.host.get(), w0, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (w1) HIPCHECK(hipMemcpyAsync(r.host.get() + 1, w1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipEventRecord(r.ev.get(), s));
     r.pending = true;
     r.sent = o;
     return SW_OK;
@@ -371,7 +382,7 @@ int readback_record(Readback& r, const Readback::Obs& o, const int32_t* w0, cons
 
 // True once per completed readback: r.host holds the words, r.last what they observe.
 bool readback_take(Readback& r) {
-    if (!r.pending || hipEventQuery(r.ev) != hipSuccess) return false;
+    if (!r.pending || hipEventQuery(r.ev.get()) != hipSuccess) return false;
     r.pending = false;
     r.seen = true;
     r.last = r.sent;
@@ -383,11 +394,6 @@ bool readback_take(Readback& r) {
 // a later scan issues: ignoring it is safe.
 void readback_reset(Readback& r) { r.pending = r.seen = false; }
 
-void readback_free(Readback& r) {
-    if (r.host) (void)hipHostFree(r.host);
-    if (r.ev) (void)hipEventDestroy(r.ev);
-    r = Readback{};
-}
 }  // namespace
 
 struct sw_db {
@@ -397,33 +403,71 @@ struct sw_db {
     int32_t max_len = 0;
     int32_t max_id = -1;
     int32_t long_threshold = 0;
-    // inter part
+    // sw_scan_lpt work tables (longest first), per scan shape
+    struct LptTable {
+        int32_t qpad, rows /* per pass */, qpad_intra, ri, npair, group /* quad blocks */, tail /* tail-pair blocks */, n;
+        bool affine;
+        bool tri;  // the group blocks by 3-wave groups with a spare wave (InterArgs::blk_tri)
+        int32_t npipe;  // the longest pairs, in the pipelined form
+        int32_t pipe_opt;  // sw_opts lpt_pipe the table was built under
+        int32_t pipe_tail;  // pairs [pipe_tail, ...) pipelined too (the shortest)
+        int32_t tail_opt;   // sw_opts lpt_pipe_tail the table was built under
+        DevPtr<int32_t> d_order;
+        std::vector<float> cost;  // estimated duration of each entry, longest first
+    };
+    static constexpr int kDrainSlots = 32;
+    // Everything that belongs to one packed layout (one long threshold):
+    // build_db and the scans after it fill it, free_dev replaces it with a
+    // fresh one.  What a member of sw_db outside it holds survives a rebuild.
+    struct Layout {
+        // inter part
+        DevPtr<uint8_t> d_res;
+        DevPtr<uint64_t> d_blk_off;
+        DevPtr<uint32_t> d_blk_groups;
+        DevPtr<uint32_t> d_blk_cols;  // block widths rounded to 8 columns (sw_inter_x2s)
+        DevPtr<int32_t> d_lane_ids;
+        DevPtr<int32_t> d_ids;        // every subject's result id (sw_scan_topk), on first use
+        DevPtr<int32_t> d_bnd_h, d_bnd_f;
+        // two rescue lists [count, block ids...] of nblocks + 1 ints each: the
+        // 16-bit kernels' flagged blocks (list A), and the fp16 chain's second
+        // stage's (list B)
+        // (two parities of these lists: consecutive scans of a batch alternate)
+        DevPtr<int32_t> d_rescue;
+        DevPtr<int32_t> d_lrescue;    // [count, subjects...] x 2: the intra rescue chain's lists
+        // boundary rows of deferred rescue tails (inter H, F; intra H, F), when
+        // device memory allows them (else the tails run in stream order)
+        DevPtr<int32_t> d_rbnd_h, d_rbnd_f, d_rlbnd_h, d_rlbnd_f;
+        bool rbnd_tried = false;
+        // intra part (long subjects)
+        DevPtr<uint8_t> d_lres;
+        DevPtr<uint64_t> d_loff;
+        DevPtr<int32_t> d_llen, d_lid, d_lbnd_h, d_lbnd_f;
+        std::vector<LptTable> lpt_tables;
+        // device copies of the merged launch's drain arguments (swk::DrainArgs),
+        // one per distinct content (profile slot x list parity x score buffer
+        // x query shape): uploaded once, then reused with no copy per scan
+        DevPtr<swk::DrainArgs> d_drain;
+        HostPtr<swk::DrainArgs> h_drain;  // pinned: the copies' sources
+        std::vector<std::vector<uint64_t>> drain_keys;  // what each slot's content is a function of
+        int drain_next = 0;
+        HostPtr<uint64_t> h_trace;  // sw_opts trace_file: host-mapped block timeline
+        size_t trace_entries = 0;   // ... its entries: per block, then per merged-launch workgroup
+        bool built = false;
+        size_t device_bytes = 0;
+    };
+    Layout lay;
+    // what build_db derives with it (overwritten by the next build)
     int64_t nblocks = 0;
     int64_t packed_cells = 0;
-    uint8_t* d_res = nullptr;
     size_t res_bytes = 0;
-    uint64_t* d_blk_off = nullptr;
-    uint32_t* d_blk_groups = nullptr;
-    uint32_t* d_blk_cols = nullptr;      // block widths rounded to 8 columns (sw_inter_x2s)
-    int32_t* d_lane_ids = nullptr;
-    int32_t* d_ids = nullptr;            // every subject's result id (sw_scan_topk), on first use
+    int64_t nlong = 0;
+    int32_t long_max = 0;
+    size_t lres_bytes = 0;
+    std::vector<uint32_t> h_blk_groups;  // block widths (16-column groups), widest first
+    std::vector<int64_t> h_blk_res;      // unpadded residues per block
+    std::vector<int32_t> h_llen;         // long subjects' lengths, longest first
     int rid_identity = -1;               // result ids are 0 .. n-1 in order (1), or not (0); -1 unknown
-    int32_t* d_bnd_h = nullptr;
-    int32_t* d_bnd_f = nullptr;
-    // two rescue lists [count, block ids...] of nblocks + 1 ints each: the
-    // 16-bit kernels' flagged blocks (list A), and the fp16 chain's second
-    // stage's (list B)
-    // (two parities of these lists: consecutive scans of a batch alternate)
-    int32_t* d_rescue = nullptr;
-    int32_t* d_lrescue = nullptr;        // [count, subjects...] x 2: the intra rescue chain's lists
     uint64_t list_epoch = 0;             // g_fault_epoch when the lists were last known clean
-    // boundary rows of deferred rescue tails (inter H, F; intra H, F), when
-    // device memory allows them (else the tails run in stream order)
-    int32_t* d_rbnd_h = nullptr;
-    int32_t* d_rbnd_f = nullptr;
-    int32_t* d_rlbnd_h = nullptr;
-    int32_t* d_rlbnd_f = nullptr;
-    bool rbnd_tried = false;
     // the intra chain's order (adapt_intra_i16_first): the fp16 pass's
     // flagged count (lcount), and per scoring the shortest query seen to flag
     // over a third of the long subjects
@@ -439,52 +483,14 @@ struct sw_db {
         int32_t span;
     };
     std::vector<SpanObs> i16_span;
-    uint64_t* h_trace = nullptr;         // sw_opts trace_file: host-mapped block timeline
-    size_t trace_entries = 0;            // ... its entries: per block, then per merged-launch workgroup
-    std::vector<uint32_t> h_blk_groups;  // block widths (16-column groups), widest first
-    std::vector<int64_t> h_blk_res;      // unpadded residues per block
     int32_t last_ncoop = 0;              // blocks the last scan gave the coop kernel
     int32_t last_npair = 0;              // blocks the last scan ran by wave pairs
-    std::vector<int32_t> h_llen;         // long subjects' lengths, longest first
-    // sw_scan_lpt work tables (longest first), per scan shape
-    struct LptTable {
-        int32_t qpad, rows /* per pass */, qpad_intra, ri, npair, group /* quad blocks */, tail /* tail-pair blocks */, n;
-        bool affine;
-        bool tri;  // the group blocks by 3-wave groups with a spare wave (InterArgs::blk_tri)
-        int32_t npipe;  // the longest pairs, in the pipelined form
-        int32_t pipe_opt;  // sw_opts lpt_pipe the table was built under
-        int32_t pipe_tail;  // pairs [pipe_tail, ...) pipelined too (the shortest)
-        int32_t tail_opt;   // sw_opts lpt_pipe_tail the table was built under
-        int32_t* d_order;
-        std::vector<float> cost;  // estimated duration of each entry, longest first
-    };
-    std::vector<LptTable> lpt_tables;
     bool last_pair_merged = false;
-    // device copies of the merged launch's drain arguments (swk::DrainArgs),
-    // one per distinct content (profile slot x list parity x score buffer
-    // x query shape): uploaded once, then reused with no copy per scan
-    static constexpr int kDrainSlots = 32;
-    swk::DrainArgs* d_drain = nullptr;
-    swk::DrainArgs* h_drain = nullptr;   // pinned: the copies' sources
-    std::vector<std::vector<uint64_t>> drain_keys;  // what each slot's content is a function of
-    int drain_next = 0;
-    // intra part (long subjects)
-    int64_t nlong = 0;
-    int32_t long_max = 0;
-    uint8_t* d_lres = nullptr;
-    size_t lres_bytes = 0;
-    uint64_t* d_loff = nullptr;
-    int32_t* d_llen = nullptr;
-    int32_t* d_lid = nullptr;
-    int32_t* d_lbnd_h = nullptr;
-    int32_t* d_lbnd_f = nullptr;
     // host copies kept to allow re-partitioning when the threshold changes
     std::vector<uint8_t, NoInitAlloc<uint8_t>> h_residues;
     std::vector<int64_t> h_offsets;
     std::vector<int32_t> h_ids;
     std::unordered_map<int32_t, int64_t> id_index;  // result id -> subject (built on first sw_align)
-    bool built = false;
-    size_t device_bytes = 0;
     // synthetic database (sw_db_create_synthetic): residues are generated
     // on the device from (seed, id_base + local id); h_residues stays empty
     bool synthetic = false;
@@ -499,7 +505,7 @@ struct sw_pssm {
     sw_handle* h = nullptr;
     int32_t qlen = 0;
     int32_t ld = 0;               // entries per code row of the image (>= qlen)
-    int8_t* d = nullptr;          // [25][ld]
+    DevPtr<int8_t> d;             // [25][ld]
     std::vector<int8_t> image;    // the upload's source (alive while the copy may run)
     int max_entry = 0;            // the largest entry (0 for an empty table)
     uint64_t hash = 0;            // FNV-1a of the [qlen][25] table
@@ -534,7 +540,7 @@ swplan::PlanDb plan_view(const sw_db* db) {
 // here once its readback has completed (long_pass records it).  opt =
 // sw_opts intra_i16_first: 0 / 1 never / always, else the observations.
 bool adapt_intra_i16_first(sw_db* db, uint64_t skey, int32_t qlen, int32_t opt) {
-    if (readback_take(db->lcount) && 3 * static_cast<int64_t>(db->lcount.host[0]) > db->nlong) {
+    if (readback_take(db->lcount) && 3 * static_cast<int64_t>(db->lcount.host.get()[0]) > db->nlong) {
         const Readback::Obs& o = db->lcount.last;
         bool seen = false;
         for (auto& e : db->i16_first)
@@ -560,7 +566,7 @@ bool adapt_intra_i16_first(sw_db* db, uint64_t skey, int32_t qlen, int32_t opt) 
 int32_t adapt_inter_i16_span(sw_db* db, uint64_t skey, int32_t qlen, int32_t opt) {
     if (readback_take(db->icount)) {
         const Readback::Obs& o = db->icount.last;
-        const int32_t cnt = db->icount.host[0], span = db->icount.host[1] + 1;
+        const int32_t cnt = db->icount.host.get()[0], span = db->icount.host.get()[1] + 1;
         // most of [nr, span) flagged: not a few high-scoring hits far out
         if (cnt > 0 && span > o.nr && 2 * static_cast<int64_t>(cnt) >= span - o.nr) {
             // keep a staircase per scoring: drop what the new observation
@@ -589,44 +595,26 @@ int32_t adapt_inter_i16_span(sw_db* db, uint64_t skey, int32_t qlen, int32_t opt
     return static_cast<int32_t>(std::min<int64_t>(std::max(i16_span, 0), db->nblocks));
 }
 
-void free_dev(sw_db* db) {
-    void* ptrs[] = {db->d_res, db->d_blk_off, db->d_blk_groups, db->d_blk_cols, db->d_lane_ids, db->d_bnd_h, db->d_bnd_f,
-                    db->d_rescue, db->d_lres, db->d_loff, db->d_llen, db->d_lid, db->d_lbnd_h, db->d_lbnd_f,
-                    db->d_lrescue, db->d_rbnd_h, db->d_rbnd_f, db->d_rlbnd_h, db->d_rlbnd_f, db->d_ids};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    db->d_res = nullptr; db->d_blk_off = nullptr; db->d_blk_groups = nullptr; db->d_lane_ids = nullptr;
-    db->d_blk_cols = nullptr;
-    db->d_bnd_h = nullptr; db->d_bnd_f = nullptr; db->d_rescue = nullptr; db->d_lres = nullptr; db->d_loff = nullptr;
-    db->d_llen = nullptr; db->d_lid = nullptr; db->d_lbnd_h = nullptr; db->d_lbnd_f = nullptr;
-    db->d_lrescue = nullptr;
-    db->d_rbnd_h = db->d_rbnd_f = db->d_rlbnd_h = db->d_rlbnd_f = nullptr;
-    db->d_ids = nullptr;
-    db->rbnd_tried = false;
-    for (auto& t : db->lpt_tables) (void)hipFree(t.d_order);
-    db->lpt_tables.clear();
-    if (db->d_drain) (void)hipFree(db->d_drain);
-    if (db->h_drain) (void)hipHostFree(db->h_drain);
-    db->d_drain = nullptr;
-    db->h_drain = nullptr;
-    db->drain_keys.clear();
-    db->drain_next = 0;
-    if (db->h_trace) (void)hipHostFree(db->h_trace);  // sized for this block layout
-    db->h_trace = nullptr;
-    db->trace_entries = 0;
+// sw_db_reset_adaptive: forget what earlier scans observed.
+void reset_adaptive(sw_db* db) {
     readback_reset(db->lcount);
-    db->i16_first.clear();  // the long partition may change
+    db->i16_first.clear();
     readback_reset(db->icount);
-    db->i16_span.clear();   // ... and the block layout
-    db->device_bytes = 0;
-    db->built = false;
+    db->i16_span.clear();
+}
+
+// Release the packed layout (the caller has quiesced the handle) and forget
+// what earlier scans observed on it.
+void free_dev(sw_db* db) {
+    db->lay = sw_db::Layout{};
+    reset_adaptive(db);  // the long partition and the block layout may change
 }
 
 template <class T>
-int upload(T** dptr, const std::vector<T>& v, hipStream_t s, size_t* acc) {
-    if (v.empty()) { *dptr = nullptr; return SW_OK; }
-    HIPCHECK(hipMalloc(reinterpret_cast<void**>(dptr), v.size() * sizeof(T)));
-    HIPCHECK(hipMemcpyAsync(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
+int upload(DevPtr<T>& d, const std::vector<T>& v, hipStream_t s, size_t* acc) {
+    if (v.empty()) return SW_OK;
+    HIPCHECK(swk::dev_alloc(d, v.size() * sizeof(T)));
+    HIPCHECK(hipMemcpyAsync(d.get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
     *acc += v.size() * sizeof(T);
     return SW_OK;
 }
@@ -734,26 +722,25 @@ int staged_upload(sw_handle* h, uint8_t* dev, const std::vector<uint64_t>& bound
     const size_t cap = std::max<size_t>(kStageBytes, maxu);
     if (cap > h->stage_cap) {
         for (int b = 0; b < 2; ++b) {
-            if (h->stage_pending[b]) HIPCHECK(hipEventSynchronize(h->stage_ev[b]));
+            if (h->stage_pending[b]) HIPCHECK(hipEventSynchronize(h->stage_ev[b].get()));
             h->stage_pending[b] = false;
-            if (h->stage[b]) HIPCHECK(hipHostFree(h->stage[b]));
-            h->stage[b] = nullptr;
+            h->stage[b].reset();
         }
         h->stage_cap = 0;
         for (int b = 0; b < 2; ++b)
-            HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&h->stage[b]), cap, hipHostMallocDefault));
+            HIPCHECK(swk::host_alloc(h->stage[b], cap, hipHostMallocDefault));
         h->stage_cap = cap;
     }
     int b = 0;
     for (int64_t u0 = 0; u0 < nu;) {
         int64_t u1 = u0 + 1;
         while (u1 < nu && bounds[u1 + 1] - bounds[u0] <= h->stage_cap) ++u1;
-        if (h->stage_pending[b]) HIPCHECK(hipEventSynchronize(h->stage_ev[b]));
-        uint8_t* buf = h->stage[b];
+        if (h->stage_pending[b]) HIPCHECK(hipEventSynchronize(h->stage_ev[b].get()));
+        uint8_t* buf = h->stage[b].get();
         const uint64_t base = bounds[u0];
         parallel_for(u1 - u0, [&](int64_t i) { fill(u0 + i, buf + (bounds[u0 + i] - base)); }, 1);
-        HIPCHECK(hipMemcpyAsync(dev + base, buf, bounds[u1] - base, hipMemcpyHostToDevice, h->stream));
-        HIPCHECK(hipEventRecord(h->stage_ev[b], h->stream));
+        HIPCHECK(hipMemcpyAsync(dev + base, buf, bounds[u1] - base, hipMemcpyHostToDevice, h->stream.get()));
+        HIPCHECK(hipEventRecord(h->stage_ev[b].get(), h->stream.get()));
         h->stage_pending[b] = true;
         b ^= 1;
         u0 = u1;
@@ -765,7 +752,7 @@ int staged_upload(sw_handle* h, uint8_t* dev, const std::vector<uint64_t>& bound
 // threshold to the intra kernel, deal the rest into 64-lane blocks of
 // 16-residue groups.  Lanes past a subject's end hold kPadCode.
 int build_db(sw_db* db) {
-    hipStream_t s = db->h->stream;
+    hipStream_t s = db->h->stream.get();
     const int64_t n = db->n;
     const std::vector<int64_t> order = length_order(db->h_offsets, n);
     auto len = [&](int64_t k) { return db->h_offsets[k + 1] - db->h_offsets[k]; };
@@ -843,58 +830,56 @@ int build_db(sw_db* db) {
     if (db->synthetic) {
         // residues generated in HBM from (seed, global id); ids in lane_ids
         // and lid are local (0..n-1), global = id_base + local
-        if (total) HIPCHECK(hipMalloc(reinterpret_cast<void**>(&db->d_res), total));
-        if (ltotal) HIPCHECK(hipMalloc(reinterpret_cast<void**>(&db->d_lres), ltotal));
+        if (total) HIPCHECK(swk::dev_alloc(db->lay.d_res, total));
+        if (ltotal) HIPCHECK(swk::dev_alloc(db->lay.d_lres, ltotal));
         acc += total + ltotal;
     } else {
         // residues through pinned staging, packed in parallel chunks
         std::vector<uint64_t> bounds(blk_off);
         bounds.push_back(total);
         if (total) {
-            HIPCHECK(hipMalloc(reinterpret_cast<void**>(&db->d_res), total));
-            if ((rc = staged_upload(db->h, db->d_res, bounds, fill_block))) return rc;
+            HIPCHECK(swk::dev_alloc(db->lay.d_res, total));
+            if ((rc = staged_upload(db->h, db->lay.d_res.get(), bounds, fill_block))) return rc;
         }
         if (ltotal) {
-            HIPCHECK(hipMalloc(reinterpret_cast<void**>(&db->d_lres), ltotal));
-            if ((rc = staged_upload(db->h, db->d_lres, loff, fill_long))) return rc;
+            HIPCHECK(swk::dev_alloc(db->lay.d_lres, ltotal));
+            if ((rc = staged_upload(db->h, db->lay.d_lres.get(), loff, fill_long))) return rc;
         }
         acc += total + ltotal;
     }
-    if ((rc = upload(&db->d_blk_off, blk_off, s, &acc))) return rc;
-    if ((rc = upload(&db->d_blk_groups, blk_groups, s, &acc))) return rc;
-    if ((rc = upload(&db->d_blk_cols, blk_cols, s, &acc))) return rc;
-    if ((rc = upload(&db->d_lane_ids, lane_ids, s, &acc))) return rc;
+    if ((rc = upload(db->lay.d_blk_off, blk_off, s, &acc))) return rc;
+    if ((rc = upload(db->lay.d_blk_groups, blk_groups, s, &acc))) return rc;
+    if ((rc = upload(db->lay.d_blk_cols, blk_cols, s, &acc))) return rc;
+    if ((rc = upload(db->lay.d_lane_ids, lane_ids, s, &acc))) return rc;
     loff.pop_back();
-    if ((rc = upload(&db->d_loff, loff, s, &acc))) return rc;
-    if ((rc = upload(&db->d_llen, llen, s, &acc))) return rc;
-    if ((rc = upload(&db->d_lid, lid, s, &acc))) return rc;
+    if ((rc = upload(db->lay.d_loff, loff, s, &acc))) return rc;
+    if ((rc = upload(db->lay.d_llen, llen, s, &acc))) return rc;
+    if ((rc = upload(db->lay.d_lid, lid, s, &acc))) return rc;
     if (db->synthetic) {
-        int32_t* d_lane_len = nullptr;
-        uint8_t* d_lut = nullptr;
+        DevPtr<int32_t> d_lane_len;  // the fill's inputs, released after it has run
+        DevPtr<uint8_t> d_lut;
         size_t tmp = 0;
-        if ((rc = upload(&d_lane_len, lane_len, s, &tmp))) return rc;
+        if ((rc = upload(d_lane_len, lane_len, s, &tmp))) return rc;
         const SynthTables& T = synth_tables();
-        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&d_lut), sizeof T.lut_stored));
-        HIPCHECK(hipMemcpyAsync(d_lut, T.lut_stored, sizeof T.lut_stored, hipMemcpyHostToDevice, s));
+        HIPCHECK(swk::dev_alloc(d_lut, sizeof T.lut_stored));
+        HIPCHECK(hipMemcpyAsync(d_lut.get(), T.lut_stored, sizeof T.lut_stored, hipMemcpyHostToDevice, s));
         swk::SynthFill f{};
-        f.res = db->d_res;
-        f.blk_off = db->d_blk_off;
-        f.blk_groups = db->d_blk_groups;
-        f.lane_local = db->d_lane_ids;
-        f.lane_len = d_lane_len;
+        f.res = db->lay.d_res.get();
+        f.blk_off = db->lay.d_blk_off.get();
+        f.blk_groups = db->lay.d_blk_groups.get();
+        f.lane_local = db->lay.d_lane_ids.get();
+        f.lane_len = d_lane_len.get();
         f.nblocks = nblocks;
-        f.lres = db->d_lres;
-        f.loff = db->d_loff;
-        f.llen = db->d_llen;
-        f.lid = db->d_lid;
+        f.lres = db->lay.d_lres.get();
+        f.loff = db->lay.d_loff.get();
+        f.llen = db->lay.d_llen.get();
+        f.lid = db->lay.d_lid.get();
         f.nlong = static_cast<int32_t>(nlong);
         f.seed = db->seed;
         f.id_base = db->id_base;
-        f.lut = d_lut;
+        f.lut = d_lut.get();
         HIPCHECK(swk::launch_synth_fill(f, s));
         HIPCHECK(hipStreamSynchronize(s));
-        if (d_lane_len) HIPCHECK(hipFree(d_lane_len));
-        HIPCHECK(hipFree(d_lut));
     }
     HIPCHECK(hipStreamSynchronize(s));  // host vectors go out of scope
     db->h_blk_groups = blk_groups;
@@ -906,30 +891,25 @@ int build_db(sw_db* db) {
     db->nlong = nlong;
     db->long_max = nlong ? static_cast<int32_t>(len(order[0])) : 0;
     db->packed_cells = static_cast<int64_t>(total);  // one byte per scanned (lane, column)
-    db->device_bytes = acc;
-    db->built = true;
+    db->lay.device_bytes = acc;
+    db->lay.built = true;
     return SW_OK;
 }
 
 // Boundary rows are only needed when the query spans more than one strip;
 // allocate on first need and keep.
 int ensure_bnd(sw_db* db, bool affine, bool intra_f) {
-    if (db->res_bytes && !db->d_bnd_h) {
-        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&db->d_bnd_h), db->res_bytes * 4));
-        db->device_bytes += db->res_bytes * 4;
-    }
-    if (affine && db->res_bytes && !db->d_bnd_f) {
-        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&db->d_bnd_f), db->res_bytes * 4));
-        db->device_bytes += db->res_bytes * 4;
-    }
-    if (db->lres_bytes && !db->d_lbnd_h) {
-        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&db->d_lbnd_h), db->lres_bytes * 4));
-        db->device_bytes += db->lres_bytes * 4;
-    }
-    if ((affine || intra_f) && db->lres_bytes && !db->d_lbnd_f) {
-        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&db->d_lbnd_f), db->lres_bytes * 4));
-        db->device_bytes += db->lres_bytes * 4;
-    }
+    const size_t res = db->res_bytes * 4, lres = db->lres_bytes * 4;
+    const struct {
+        DevPtr<int32_t>& p;
+        size_t bytes;
+    } rows[] = {{db->lay.d_bnd_h, res}, {db->lay.d_bnd_f, affine ? res : 0},
+                {db->lay.d_lbnd_h, lres}, {db->lay.d_lbnd_f, (affine || intra_f) ? lres : 0}};
+    for (const auto& r : rows)
+        if (r.bytes && !r.p.get()) {
+            HIPCHECK(swk::dev_alloc(r.p, r.bytes));
+            db->lay.device_bytes += r.bytes;
+        }
     return SW_OK;
 }
 
@@ -939,29 +919,27 @@ int ensure_bnd(sw_db* db, bool affine, bool intra_f) {
 // would drop below a quarter of the card's (a 50M-subject database keeps its
 // tails in stream order); a refused size is not tried again for this layout.
 bool ensure_rbnd(sw_db* db, bool affine, bool intra_f) {
-    void** p[4] = {reinterpret_cast<void**>(&db->d_rbnd_h), reinterpret_cast<void**>(&db->d_rbnd_f),
-                   reinterpret_cast<void**>(&db->d_rlbnd_h), reinterpret_cast<void**>(&db->d_rlbnd_f)};
+    DevPtr<int32_t>* const p[4] = {&db->lay.d_rbnd_h, &db->lay.d_rbnd_f, &db->lay.d_rlbnd_h, &db->lay.d_rlbnd_f};
     const size_t sz[4] = {db->res_bytes * 4, affine ? db->res_bytes * 4 : 0, db->lres_bytes * 4,
                           (affine || intra_f) ? db->lres_bytes * 4 : 0};
     size_t need = 0;
     for (int k = 0; k < 4; ++k)
-        if (sz[k] && !*p[k]) need += sz[k];
+        if (sz[k] && !p[k]->get()) need += sz[k];
     if (need == 0) return true;
-    if (db->rbnd_tried) return false;
+    if (db->lay.rbnd_tried) return false;
     size_t freeb = 0, totalb = 0;
     if (hipMemGetInfo(&freeb, &totalb) != hipSuccess || freeb < need + totalb / 4) {
-        db->rbnd_tried = true;
+        db->lay.rbnd_tried = true;
         return false;
     }
     for (int k = 0; k < 4; ++k)
-        if (sz[k] && !*p[k]) {
-            if (hipMalloc(p[k], sz[k]) != hipSuccess) {
-                *p[k] = nullptr;
+        if (sz[k] && !p[k]->get()) {
+            if (swk::dev_alloc(*p[k], sz[k]) != hipSuccess) {
                 (void)hipGetLastError();
-                db->rbnd_tried = true;
+                db->lay.rbnd_tried = true;
                 return false;
             }
-            db->device_bytes += sz[k];
+            db->lay.device_bytes += sz[k];
         }
     return true;
 }
@@ -1068,27 +1046,27 @@ int build_profiles(sw_handle* h, const QuerySrc& src, const int8_t* mat, int go,
     if (S.pending) HIPCHECK(hipEventSynchronize(S.last_end));
     S.pending = false;
     if (P->total > S.dcap) {
-        if (S.d) {
-            HIPCHECK(hipStreamSynchronize(h->stream));  // scans in flight may still read it
-            if (S.tail_pending) HIPCHECK(hipEventSynchronize(S.tail_read));
+        if (S.d.get()) {
+            HIPCHECK(hipStreamSynchronize(h->stream.get()));  // scans in flight may still read it
+            if (S.tail_pending) HIPCHECK(hipEventSynchronize(S.tail_read.get()));
             S.tail_pending = false;
-            HIPCHECK(hipFree(S.d));
+            S.d.reset();
         }
         S.dcap = std::max<size_t>(P->total, 1 << 16);
-        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&S.d), S.dcap));
+        HIPCHECK(swk::dev_alloc(S.d, S.dcap));
     }
-    P->dev = S.d;
+    P->dev = S.d.get();
     // on the scan's stream: after the scans before it (the slot's last
     // reader among them), before this one
     if (S.tail_pending) {  // a deferred tail still reads the slot's last profiles
-        HIPCHECK(hipStreamWaitEvent(h->stream, S.tail_read, 0));
+        HIPCHECK(hipStreamWaitEvent(h->stream.get(), S.tail_read.get(), 0));
         S.tail_pending = false;
     }
     if (src.pssm) {
         swk::PssmProfileArgs a{};
-        a.p8 = S.d + P->off8;
-        a.p16 = want16 ? reinterpret_cast<int16_t*>(S.d + P->off16) : nullptr;
-        a.pin = ri ? S.d + P->intra_off : nullptr;
+        a.p8 = S.d.get() + P->off8;
+        a.p16 = want16 ? reinterpret_cast<int16_t*>(S.d.get() + P->off16) : nullptr;
+        a.pin = ri ? S.d.get() + P->intra_off : nullptr;
         a.stride = P->stride;
         a.qlen = qlen;
         a.bias = bias;
@@ -1097,18 +1075,18 @@ int build_profiles(sw_handle* h, const QuerySrc& src, const int8_t* mat, int go,
         a.qpad_intra = ri ? qpad_intra : 0;
         a.rows = std::max(P->stride, a.qpad_intra);
         for (int k = 0; k < 10; ++k) a.reset[k] = reset[k];
-        a.pssm = src.pssm->d;
+        a.pssm = src.pssm->d.get();
         a.ld = src.pssm->ld;
-        HIPCHECK(swk::launch_build_profile_pssm(a, h->stream));
-        S.last_end = h->ev[3];
+        HIPCHECK(swk::launch_build_profile_pssm(a, h->stream.get()));
+        S.last_end = h->ev[3].get();
         S.pending = true;
         h->open_slot = P->slot;
         return SW_OK;
     }
     swk::ProfileArgs a{};
-    a.p8 = S.d + P->off8;
-    a.p16 = want16 ? reinterpret_cast<int16_t*>(S.d + P->off16) : nullptr;
-    a.pin = ri ? S.d + P->intra_off : nullptr;
+    a.p8 = S.d.get() + P->off8;
+    a.p16 = want16 ? reinterpret_cast<int16_t*>(S.d.get() + P->off16) : nullptr;
+    a.pin = ri ? S.d.get() + P->intra_off : nullptr;
     a.stride = P->stride;
     a.qlen = qlen;
     a.bias = bias;
@@ -1123,10 +1101,10 @@ int build_profiles(sw_handle* h, const QuerySrc& src, const int8_t* mat, int go,
         a.row1 = std::min(rows, r0 + swk::kProfQueryChunk);
         const int32_t nq = std::max(0, std::min(a.row1, qlen) - r0);
         if (nq) std::memcpy(a.q, q + r0, static_cast<size_t>(nq));
-        HIPCHECK(swk::launch_build_profile(a, h->stream));
+        HIPCHECK(swk::launch_build_profile(a, h->stream.get()));
         for (auto& p : a.reset) p = nullptr;  // once
     }
-    S.last_end = h->ev[3];  // recorded at the end of this scan (scan_impl)
+    S.last_end = h->ev[3].get();  // recorded at the end of this scan (scan_impl)
     S.pending = true;
     h->open_slot = P->slot;  // until ev[3] is recorded (scan_impl cleans up if it fails first)
     return SW_OK;
@@ -1137,7 +1115,7 @@ int build_profiles(sw_handle* h, const QuerySrc& src, const int8_t* mat, int go,
 const sw_db::LptTable* lpt_table(sw_db* db, const swplan::ScanPlan& p) {
     const sw_opts& O = db->h->opts;
     const bool tri = p.ntri != 0;
-    for (const auto& t : db->lpt_tables)
+    for (const auto& t : db->lay.lpt_tables)
         if (t.qpad == p.qpad_inter && t.rows == p.lpt_rows && t.qpad_intra == p.qpad_intra2 && t.ri == p.ri2 &&
             t.npair == p.npair && t.group == p.nquad && t.tail == p.ntail && t.pipe_opt == O.lpt_pipe &&
             t.affine == p.affine && t.tri == tri && t.tail_opt == O.lpt_pipe_tail)
@@ -1146,22 +1124,18 @@ const sw_db::LptTable* lpt_table(sw_db* db, const swplan::ScanPlan& p) {
                                                 p.nquad, p.ntail, p.affine, tri);
     sw_db::LptTable t{p.qpad_inter, p.lpt_rows, p.qpad_intra2, p.ri2, p.npair, p.nquad, p.ntail,
                       static_cast<int32_t>(pl.order.size()), p.affine, tri, pl.npipe, O.lpt_pipe, pl.pipe_tail,
-                      O.lpt_pipe_tail, nullptr, pl.cost};
+                      O.lpt_pipe_tail, DevPtr<int32_t>{}, pl.cost};
     const size_t bytes = pl.order.size() * sizeof(int32_t);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&t.d_order), bytes);
-    if (e == hipSuccess && (e = hipMemcpy(t.d_order, pl.order.data(), bytes, hipMemcpyHostToDevice)) != hipSuccess)
-        (void)hipFree(t.d_order);
+    hipError_t e = swk::dev_alloc(t.d_order, bytes);
+    if (e == hipSuccess) e = hipMemcpy(t.d_order.get(), pl.order.data(), bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         fail(SW_E_HIP, std::string("sw_scan_lpt's work table: ") + hipGetErrorString(e));
         return nullptr;
     }
-    db->device_bytes += bytes;
-    if (db->lpt_tables.size() >= 8) {
-        (void)hipFree(db->lpt_tables.front().d_order);
-        db->lpt_tables.erase(db->lpt_tables.begin());
-    }
-    db->lpt_tables.push_back(std::move(t));
-    return &db->lpt_tables.back();
+    db->lay.device_bytes += bytes;
+    if (db->lay.lpt_tables.size() >= 8) db->lay.lpt_tables.erase(db->lay.lpt_tables.begin());
+    db->lay.lpt_tables.push_back(std::move(t));
+    return &db->lay.lpt_tables.back();
 }
 
 // The device copy of a merged launch's drain arguments (swk::DrainArgs: read
@@ -1172,26 +1146,27 @@ const sw_db::LptTable* lpt_table(sw_db* db, const swplan::ScanPlan& p) {
 // scan of a steady loop after the first few) costs no copy.
 int drain_blob(sw_db* db, hipStream_t s, const std::vector<uint64_t>& key, const swk::DrainArgs& d,
                const swk::DrainArgs** out) {
-    if (!db->d_drain) {
-        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&db->d_drain), sw_db::kDrainSlots * sizeof(swk::DrainArgs)));
-        HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&db->h_drain), sw_db::kDrainSlots * sizeof(swk::DrainArgs),
-                               hipHostMallocDefault));
-        db->device_bytes += sw_db::kDrainSlots * sizeof(swk::DrainArgs);
+    if (!db->lay.d_drain.get()) {  // both or neither
+        DevPtr<swk::DrainArgs> dev;
+        HIPCHECK(swk::dev_alloc(dev, sw_db::kDrainSlots * sizeof(swk::DrainArgs)));
+        HIPCHECK(swk::host_alloc(db->lay.h_drain, sw_db::kDrainSlots * sizeof(swk::DrainArgs), hipHostMallocDefault));
+        db->lay.d_drain = std::move(dev);
+        db->lay.device_bytes += sw_db::kDrainSlots * sizeof(swk::DrainArgs);
     }
-    for (size_t k = 0; k < db->drain_keys.size(); ++k)
-        if (db->drain_keys[k] == key) {
-            *out = db->d_drain + k;
+    for (size_t k = 0; k < db->lay.drain_keys.size(); ++k)
+        if (db->lay.drain_keys[k] == key) {
+            *out = db->lay.d_drain.get() + k;
             return SW_OK;
         }
     // a slot is rewritten only after the 31 uploads since its last one, each
     // in stream order behind the scans that read it
-    const int k = db->drain_next;
-    db->drain_next = (k + 1) % sw_db::kDrainSlots;
-    if (static_cast<int>(db->drain_keys.size()) <= k) db->drain_keys.resize(k + 1);
-    db->drain_keys[k] = key;
-    db->h_drain[k] = d;
-    HIPCHECK(hipMemcpyAsync(db->d_drain + k, &db->h_drain[k], sizeof d, hipMemcpyHostToDevice, s));
-    *out = db->d_drain + k;
+    const int k = db->lay.drain_next;
+    db->lay.drain_next = (k + 1) % sw_db::kDrainSlots;
+    if (static_cast<int>(db->lay.drain_keys.size()) <= k) db->lay.drain_keys.resize(k + 1);
+    db->lay.drain_keys[k] = key;
+    db->lay.h_drain.get()[k] = d;
+    HIPCHECK(hipMemcpyAsync(db->lay.d_drain.get() + k, &db->lay.h_drain.get()[k], sizeof d, hipMemcpyHostToDevice, s));
+    *out = db->lay.d_drain.get() + k;
     return SW_OK;
 }
 
@@ -1201,7 +1176,7 @@ int drain_blob(sw_db* db, hipStream_t s, const std::vector<uint64_t>& key, const
 int join_tails(sw_handle* h) {
     for (int q = 0; q < 2; ++q)
         if (h->tail_pending[q]) {
-            HIPCHECK(hipStreamWaitEvent(h->stream, h->tail_done[q], 0));
+            HIPCHECK(hipStreamWaitEvent(h->stream.get(), h->tail_done[q].get(), 0));
             h->tail_pending[q] = false;
         }
     return SW_OK;
@@ -1218,7 +1193,7 @@ struct RankReq {
 };
 
 // The ranking input over a database's subjects: its scores through the
-// result ids (db->d_ids, uploaded on first use), or directly when the ids
+// result ids (db->lay.d_ids.get(), uploaded on first use), or directly when the ids
 // are 0 .. n-1 in order (the default).
 int rank_src(sw_db* db, const int32_t* scores, const RankReq& rq, swk::TopkSrc* src) {
     if (db->rid_identity < 0) {
@@ -1230,13 +1205,13 @@ int rank_src(sw_db* db, const int32_t* scores, const RankReq& rq, swk::TopkSrc* 
     src->gid = rq.gid;
     src->id_base = rq.id_base;
     if (!db->rid_identity) {
-        if (!db->d_ids) {
-            HIPCHECK(hipMalloc(reinterpret_cast<void**>(&db->d_ids), static_cast<size_t>(db->n) * sizeof(int32_t)));
-            HIPCHECK(hipMemcpy(db->d_ids, db->h_ids.data(), static_cast<size_t>(db->n) * sizeof(int32_t),
+        if (!db->lay.d_ids.get()) {
+            HIPCHECK(swk::dev_alloc(db->lay.d_ids, static_cast<size_t>(db->n) * sizeof(int32_t)));
+            HIPCHECK(hipMemcpy(db->lay.d_ids.get(), db->h_ids.data(), static_cast<size_t>(db->n) * sizeof(int32_t),
                                hipMemcpyHostToDevice));
-            db->device_bytes += static_cast<size_t>(db->n) * sizeof(int32_t);
+            db->lay.device_bytes += static_cast<size_t>(db->n) * sizeof(int32_t);
         }
-        src->rid = db->d_ids;
+        src->rid = db->lay.d_ids.get();
     }
     return SW_OK;
 }
@@ -1245,13 +1220,15 @@ int rank_src(sw_db* db, const int32_t* scores, const RankReq& rq, swk::TopkSrc* 
 // starts with the one-launch top-K's counter at zero (swk::launch_topk).
 int ensure_topk_work(sw_handle* h, size_t need) {
     if (need > h->topk_cap) {
-        if (h->d_topk_work) {
-            HIPCHECK(hipStreamSynchronize(h->stream));
-            HIPCHECK(hipFree(h->d_topk_work));
+        if (h->d_topk_work.get()) {
+            HIPCHECK(hipStreamSynchronize(h->stream.get()));
+            h->d_topk_work.reset();
         }
-        h->topk_cap = std::max<size_t>(need, 1 << 20);
-        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&h->d_topk_work), h->topk_cap));
-        HIPCHECK(hipMemsetAsync(h->d_topk_work, 0, 256, h->stream));
+        h->topk_cap = 0;
+        const size_t cap = std::max<size_t>(need, 1 << 20);
+        HIPCHECK(swk::dev_alloc(h->d_topk_work, cap));
+        h->topk_cap = cap;
+        HIPCHECK(hipMemsetAsync(h->d_topk_work.get(), 0, 256, h->stream.get()));
     }
     return SW_OK;
 }
@@ -1260,8 +1237,8 @@ int next_events(sw_handle* h) {
     if (h->nscans >= 4096) h->nscans = 0;  // bound the pool; older sums are dropped
     if (h->nscans == h->evpool.size()) {
         ScanEvents se;
-        for (auto& e : se.ev) HIPCHECK(hipEventCreate(&e));
-        h->evpool.push_back(se);
+        for (auto& e : se.ev) HIPCHECK(swk::event_create(e));
+        h->evpool.push_back(std::move(se));
     }
     h->ev = h->evpool[h->nscans].ev;
     h->ev_rec = &h->evpool[h->nscans].rec;
@@ -1279,7 +1256,7 @@ int rank_after(sw_handle* h, sw_db* db, const int32_t* scores_dev, const RankReq
     int rc;
     if ((rc = rank_src(db, scores_dev, rq, &src))) return rc;
     if ((rc = ensure_topk_work(h, swk::topk_workspace_bytes(db->n, rq.k)))) return rc;
-    HIPCHECK(swk::launch_topk(src, db->n, rq.k, rq.out, h->d_topk_work, h->stream));
+    HIPCHECK(swk::launch_topk(src, db->n, rq.k, rq.out, h->d_topk_work.get(), h->stream.get()));
     ++h->launches;
     return SW_OK;
 }
@@ -1290,9 +1267,9 @@ struct BndRows {
     int32_t *h, *f, *lh, *lf;
 };
 // ... of a scan's passes, and of the rescue tails in stream order behind them
-BndRows pass_rows(const sw_db* db) { return {db->d_bnd_h, db->d_bnd_f, db->d_lbnd_h, db->d_lbnd_f}; }
+BndRows pass_rows(const sw_db::Layout& l) { return {l.d_bnd_h.get(), l.d_bnd_f.get(), l.d_lbnd_h.get(), l.d_lbnd_f.get()}; }
 // ... of a deferred rescue tail, and of the merged launch's drain (ensure_rbnd)
-BndRows tail_rows(const sw_db* db) { return {db->d_rbnd_h, db->d_rbnd_f, db->d_rlbnd_h, db->d_rlbnd_f}; }
+BndRows tail_rows(const sw_db::Layout& l) { return {l.d_rbnd_h.get(), l.d_rbnd_f.get(), l.d_rlbnd_h.get(), l.d_rlbnd_f.get()}; }
 
 // What the stages of one scan share.
 struct Scan {
@@ -1331,10 +1308,10 @@ int scan_empty(sw_handle* h, sw_db* db, int32_t* scores_dev, bool defer, const R
     // a non-deferred scan completes on the handle's stream: so do the
     // earlier scans' deferred tails (a batch may end with an empty query)
     if (!defer && (rc = join_tails(h))) return rc;
-    MARK(0, h->stream);
-    if (db->max_id >= 0) HIPCHECK(hipMemsetAsync(scores_dev, 0, static_cast<size_t>(db->max_id + 1) * 4, h->stream));
+    MARK(0, h->stream.get());
+    if (db->max_id >= 0) HIPCHECK(hipMemsetAsync(scores_dev, 0, static_cast<size_t>(db->max_id + 1) * 4, h->stream.get()));
     if (rq && (rc = rank_after(h, db, scores_dev, *rq))) return rc;
-    for (int k = 1; k < 8; ++k) MARK(k, h->stream);
+    for (int k = 1; k < 8; ++k) MARK(k, h->stream.get());
     h->timed = true;
     return SW_OK;
 }
@@ -1351,28 +1328,29 @@ int scan_lists(Scan& c, bool defer) {
     // (sw_kernels.h: whoever takes an entry resets it)
     const int64_t rstride = 2 * (db->nblocks + 1) + 4;
     const int64_t lstride = 2 * (db->nlong + 1) + 2;  // intra lists 1 and 2, their heads
-    if (p.rescue && db->nblocks && !db->d_rescue) {
-        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&db->d_rescue), 2 * rstride * sizeof(int32_t)));
-        HIPCHECK(hipMemsetAsync(db->d_rescue, 0xff, 2 * rstride * sizeof(int32_t), h->stream));
-        db->device_bytes += 2 * rstride * sizeof(int32_t);
+    if (p.rescue && db->nblocks && !db->lay.d_rescue.get()) {
+        HIPCHECK(swk::dev_alloc(db->lay.d_rescue, 2 * rstride * sizeof(int32_t)));
+        HIPCHECK(hipMemsetAsync(db->lay.d_rescue.get(), 0xff, 2 * rstride * sizeof(int32_t), h->stream.get()));
+        db->lay.device_bytes += 2 * rstride * sizeof(int32_t);
     }
     if ((p.multi_inter || p.multi_intra) && (rc = ensure_bnd(db, p.affine, p.intra_x2))) return rc;
-    if (p.intra_x2 && !db->d_lrescue) {  // two lists: [count, subjects...] x 2
-        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&db->d_lrescue), 2 * lstride * sizeof(int32_t)));
-        HIPCHECK(hipMemsetAsync(db->d_lrescue, 0xff, 2 * lstride * sizeof(int32_t), h->stream));
-        db->device_bytes += 2 * lstride * sizeof(int32_t);
+    if (p.intra_x2 && !db->lay.d_lrescue.get()) {  // two lists: [count, subjects...] x 2
+        HIPCHECK(swk::dev_alloc(db->lay.d_lrescue, 2 * lstride * sizeof(int32_t)));
+        HIPCHECK(hipMemsetAsync(db->lay.d_lrescue.get(), 0xff, 2 * lstride * sizeof(int32_t), h->stream.get()));
+        db->lay.device_bytes += 2 * lstride * sizeof(int32_t);
     }
     if (db->list_epoch != g_fault_epoch.load()) {  // a fault since: entries may be left claimed
         if ((rc = join_tails(h))) return rc;
-        if (db->d_rescue) HIPCHECK(hipMemsetAsync(db->d_rescue, 0xff, 2 * rstride * sizeof(int32_t), h->stream));
-        if (db->d_lrescue) HIPCHECK(hipMemsetAsync(db->d_lrescue, 0xff, 2 * lstride * sizeof(int32_t), h->stream));
+        hipStream_t const s = h->stream.get();
+        if (int32_t* l = db->lay.d_rescue.get()) HIPCHECK(hipMemsetAsync(l, 0xff, 2 * rstride * sizeof(int32_t), s));
+        if (int32_t* l = db->lay.d_lrescue.get()) HIPCHECK(hipMemsetAsync(l, 0xff, 2 * lstride * sizeof(int32_t), s));
         db->list_epoch = g_fault_epoch.load();
     }
     // this scan's list set; a deferred tail of the scan before last used it
     c.par = h->parity;
     h->parity ^= 1;
     if (h->tail_pending[c.par]) {
-        HIPCHECK(hipStreamWaitEvent(h->stream, h->tail_done[c.par], 0));
+        HIPCHECK(hipStreamWaitEvent(h->stream.get(), h->tail_done[c.par].get(), 0));
         h->tail_pending[c.par] = false;
     }
     // The drain re-scores on the deferred tails' boundary rows (d_rbnd_*,
@@ -1380,15 +1358,15 @@ int scan_lists(Scan& c, bool defer) {
     // routed int16-first, say) may still be running its tail on those rows,
     // so the merged launch starts after every pending tail.
     if (p.drain && (rc = join_tails(h))) return rc;
-    if (db->d_rescue) {
-        c.listA = db->d_rescue + c.par * rstride;
+    if (db->lay.d_rescue.get()) {
+        c.listA = db->lay.d_rescue.get() + c.par * rstride;
         c.listB = c.listA + db->nblocks + 1;
         c.maxA = c.listA + 2 * (db->nblocks + 1);
         c.headA = c.maxA + 2;
         if (p.lpt && h->opts.lpt_persist != 0) c.lpt_next = c.maxA + 1;  // the spare word
     }
-    if (db->d_lrescue) {
-        c.list1 = db->d_lrescue + c.par * lstride;
+    if (db->lay.d_lrescue.get()) {
+        c.list1 = db->lay.d_lrescue.get() + c.par * lstride;
         c.list2 = c.list1 + db->nlong + 1;
         c.head1 = c.list2 + db->nlong + 1;
     }
@@ -1420,29 +1398,29 @@ int inter_args(Scan& c) {
     const swplan::ScanPlan& p = c.plan;
     const int go = c.sc.go, ge = c.sc.ge;
     swk::InterArgs& a = c.a;
-    a.residues = db->d_res;
-    a.blk_off = db->d_blk_off;
-    a.blk_groups = db->d_blk_groups;
-    a.blk_cols = db->d_blk_cols;
-    a.lane_ids = db->d_lane_ids;
+    a.residues = db->lay.d_res.get();
+    a.blk_off = db->lay.d_blk_off.get();
+    a.blk_groups = db->lay.d_blk_groups.get();
+    a.blk_cols = db->lay.d_blk_cols.get();
+    a.lane_ids = db->lay.d_lane_ids.get();
     a.nblocks = static_cast<int32_t>(db->nblocks);
     a.prof = c.P.dev + (p.shape.x2s ? c.P.off16 : c.P.off8);
     a.prof_stride = c.P.stride;
     a.qpad = p.qpad_inter;
     a.gap_open = go;
     a.gap_extend = ge;
-    a.bnd_h = db->d_bnd_h;
-    a.bnd_f = db->d_bnd_f;
+    a.bnd_h = db->lay.d_bnd_h.get();
+    a.bnd_f = db->lay.d_bnd_f.get();
     a.scores = c.scores;
     if (c.h->opts.trace_file[0]) {
-        if (!db->h_trace) {
+        if (!db->lay.h_trace.get()) {
             // one entry per block, then one per workgroup of a merged
             // launch (at most nblocks inter + nlong / 8 intra workgroups)
-            db->trace_entries = static_cast<size_t>(2 * db->nblocks + db->nlong + 8);
-            HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&db->h_trace), 32 * db->trace_entries, hipHostMallocMapped));
-            std::memset(db->h_trace, 0, 32 * db->trace_entries);
+            db->lay.trace_entries = static_cast<size_t>(2 * db->nblocks + db->nlong + 8);
+            HIPCHECK(swk::host_alloc(db->lay.h_trace, 32 * db->lay.trace_entries, hipHostMallocMapped));
+            std::memset(db->lay.h_trace.get(), 0, 32 * db->lay.trace_entries);
         }
-        HIPCHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&a.trace), db->h_trace, 0));
+        HIPCHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&a.trace), db->lay.h_trace.get(), 0));
     }
     if (p.rescue) {
         a.rescue_count = c.listA;
@@ -1487,17 +1465,17 @@ int inter_args(Scan& c) {
 void intra_args(Scan& c) {
     const sw_db* db = c.db;
     swk::IntraArgs& ia = c.ia;
-    ia.residues = db->d_lres;
-    ia.subj_off = db->d_loff;
-    ia.subj_len = db->d_llen;
-    ia.subj_id = db->d_lid;
+    ia.residues = db->lay.d_lres.get();
+    ia.subj_off = db->lay.d_loff.get();
+    ia.subj_len = db->lay.d_llen.get();
+    ia.subj_id = db->lay.d_lid.get();
     ia.nsubj = static_cast<int32_t>(db->nlong);
     ia.prof = c.P.dev + c.P.intra_off;
     ia.qpad = c.plan.qpad_intra;
     ia.gap_open = c.sc.go;
     ia.gap_extend = c.sc.ge;
-    ia.bnd_h = db->d_lbnd_h;
-    ia.bnd_f = db->d_lbnd_f;
+    ia.bnd_h = db->lay.d_lbnd_h.get();
+    ia.bnd_f = db->lay.d_lbnd_f.get();
     ia.scores = c.scores;
 }
 
@@ -1617,10 +1595,10 @@ int launch_intra_tail(Scan& c, hipStream_t st, const RescueStages& s) {
 int intra_tail(Scan& c, hipStream_t is) {
     c.intra_tail = true;
     if (c.deferred) {
-        HIPCHECK(hipEventRecord(c.h->side_done, is));
+        HIPCHECK(hipEventRecord(c.h->side_done.get(), is));
         return SW_OK;
     }
-    return launch_intra_tail(c, is, rescue_stages(c, c.x, pass_rows(c.db), false));
+    return launch_intra_tail(c, is, rescue_stages(c, c.x, pass_rows(c.db->lay), false));
 }
 
 // After every fp16 launch that appends to list A has joined the main
@@ -1631,24 +1609,24 @@ int inter_tail(Scan& c) {
     const swplan::ScanPlan& p = c.plan;
     int rc;
     if (p.f16 && p.rescue &&
-        (rc = readback_record(c.db->icount, {c.skey, c.qhash, c.qlen, p.nr}, c.listA, c.maxA, h->stream)))
+        (rc = readback_record(c.db->icount, {c.skey, c.qhash, c.qlen, p.nr}, c.listA, c.maxA, h->stream.get())))
         return rc;
     c.inter_tail = p.rescue && !p.drain;
     if (!c.inter_tail) return SW_OK;
     if (c.deferred) {
-        HIPCHECK(hipEventRecord(h->main_done, h->stream));
+        HIPCHECK(hipEventRecord(h->main_done.get(), h->stream.get()));
         return SW_OK;
     }
-    return launch_inter_tail(c, h->stream, rescue_stages(c, c.x, pass_rows(c.db), false));
+    return launch_inter_tail(c, h->stream.get(), rescue_stages(c, c.x, pass_rows(c.db->lay), false));
 }
 
 // The long subjects on the side stream, beside the inter kernels.
 int long_pass(Scan& c) {
     sw_handle* h = c.h;
     const swplan::ScanPlan& p = c.plan;
-    hipStream_t const is = h->side;
+    hipStream_t const is = h->side.get();
     int rc;
-    HIPCHECK(hipStreamWaitEvent(is, h->ev[0], 0));
+    HIPCHECK(hipStreamWaitEvent(is, h->ev[0].get(), 0));
     h->had_intra = true;
     ++h->launches;
     if (!p.intra_x2) {  // int32 over every long subject
@@ -1678,11 +1656,11 @@ int inter_pass(Scan& c) {
         k.blk_first = 0;
         k.qpad = p.qpad_coop;
         k.prof = c.P.dev + c.P.off8;  // the coop kernel reads the int8 profile
-        HIPCHECK(hipStreamWaitEvent(h->side2, h->ev[0], 0));
-        MARK(4, h->side2);
-        HIPCHECK(swk::launch_inter_coop(k, p.ncoop, p.affine, h->opts.coop_skew != 0, h->side2));
-        MARK(5, h->side2);
-        HIPCHECK(hipEventRecord(h->coop_done, h->side2));
+        HIPCHECK(hipStreamWaitEvent(h->side2.get(), h->ev[0].get(), 0));
+        MARK(4, h->side2.get());
+        HIPCHECK(swk::launch_inter_coop(k, p.ncoop, p.affine, h->opts.coop_skew != 0, h->side2.get()));
+        MARK(5, h->side2.get());
+        HIPCHECK(hipEventRecord(h->coop_done.get(), h->side2.get()));
         ++h->launches;
     } else if (p.nr) {
         // blocks [0, nr) in int16 by wave pairs beside the fp16 launch;
@@ -1694,22 +1672,22 @@ int inter_pass(Scan& c) {
         k.rescue_list = c.listB + 1;
         k.rescue_count = c.listB;
         k.rescue_max = nullptr;
-        HIPCHECK(hipEventRecord(h->fork2, h->stream));
-        HIPCHECK(hipStreamWaitEvent(h->side2, h->fork2, 0));
-        MARK(4, h->side2);
-        HIPCHECK(swk::launch_inter_x2p(k, p.affine, false, false, 2, h->side2));
-        MARK(5, h->side2);
-        HIPCHECK(hipEventRecord(h->coop_done, h->side2));
+        HIPCHECK(hipEventRecord(h->fork2.get(), h->stream.get()));
+        HIPCHECK(hipStreamWaitEvent(h->side2.get(), h->fork2.get(), 0));
+        MARK(4, h->side2.get());
+        HIPCHECK(swk::launch_inter_x2p(k, p.affine, false, false, 2, h->side2.get()));
+        MARK(5, h->side2.get());
+        HIPCHECK(hipEventRecord(h->coop_done.get(), h->side2.get()));
         ++h->launches;
     }
-    MARK(6, h->stream);
+    MARK(6, h->stream.get());
     if (p.npair)  // one launch: pairs for blocks [nr, npair), one wave per block after
-        HIPCHECK(swk::launch_inter_x2p(c.a, p.affine, p.f16, true, swplan::pair_group(plan_view(c.db)), h->stream));
+        HIPCHECK(swk::launch_inter_x2p(c.a, p.affine, p.f16, true, swplan::pair_group(plan_view(c.db)), h->stream.get()));
     else
-        HIPCHECK(swk::launch_inter(c.a, p.affine, p.shape, h->stream));
-    MARK(7, h->stream);
+        HIPCHECK(swk::launch_inter(c.a, p.affine, p.shape, h->stream.get()));
+    MARK(7, h->stream.get());
     ++h->launches;
-    if (p.ncoop || p.nr) HIPCHECK(hipStreamWaitEvent(h->stream, h->coop_done, 0));
+    if (p.ncoop || p.nr) HIPCHECK(hipStreamWaitEvent(h->stream.get(), h->coop_done.get(), 0));
     return inter_tail(c);
 }
 
@@ -1717,7 +1695,7 @@ int inter_pass(Scan& c) {
 // stages on the tails' boundary rows, as a device blob (drain_blob).
 int drain_args(Scan& c, const swk::IntraArgs& x, const sw_db::LptTable& t, const swk::DrainArgs** out) {
     const swplan::ScanPlan& p = c.plan;
-    const RescueStages s = rescue_stages(c, x, tail_rows(c.db), true);
+    const RescueStages s = rescue_stages(c, x, tail_rows(c.db->lay), true);
     swk::DrainArgs d{};
     d.a16 = s.a16;
     d.a32 = s.a32;
@@ -1744,7 +1722,7 @@ int drain_args(Scan& c, const swk::IntraArgs& x, const sw_db::LptTable& t, const
         static_cast<uint64_t>(p.ri2) | static_cast<uint64_t>(p.lpt_rows) << 16 | static_cast<uint64_t>(t.npipe) << 32,
         static_cast<uint64_t>(static_cast<uint32_t>(t.pipe_tail)),
         static_cast<uint64_t>(static_cast<uint32_t>(d.spin))};
-    return drain_blob(c.db, c.h->stream, key, d, out);
+    return drain_blob(c.db, c.h->stream.get(), key, d, out);
 }
 
 // One launch on the main stream: the inter groups + single waves and the
@@ -1755,7 +1733,7 @@ int merged_pass(Scan& c) {
     const swplan::ScanPlan& p = c.plan;
     int rc;
     h->had_intra = true;
-    MARK(6, h->stream);
+    MARK(6, h->stream.get());
     const sw_db::LptTable* t = lpt_table(c.db, p);
     if (!t) return SW_E_HIP;
     swk::IntraArgs x = c.x;
@@ -1763,14 +1741,14 @@ int merged_pass(Scan& c) {
     x.pipe_tail = t->pipe_tail;
     const swk::DrainArgs* dargs = nullptr;
     if (p.drain && (rc = drain_args(c, x, *t, &dargs))) return rc;
-    HIPCHECK(swk::launch_scan_lpt(c.a, x, t->d_order, t->n, p.affine, p.ri2, h->cus, h->stream, dargs, c.lpt_next,
-                                  h->opts.lpt_persist >= 2 ? h->opts.lpt_persist : 0, p.lpt_rows));
+    HIPCHECK(swk::launch_scan_lpt(c.a, x, t->d_order.get(), t->n, p.affine, p.ri2, h->cus, h->stream.get(), dargs,
+                                  c.lpt_next, h->opts.lpt_persist >= 2 ? h->opts.lpt_persist : 0, p.lpt_rows));
     ++h->launches;
     // (a draining launch ends the scan: its end event is ev[3])
-    if (!p.drain) MARK(7, h->stream);
+    if (!p.drain) MARK(7, h->stream.get());
     // the fp16 pass's flagged count, as long_pass's
-    if ((rc = readback_record(c.db->lcount, {c.skey, c.qhash, c.qlen, 0}, c.list1, nullptr, h->stream))) return rc;
-    if (!p.drain && (rc = intra_tail(c, h->stream))) return rc;
+    if ((rc = readback_record(c.db->lcount, {c.skey, c.qhash, c.qlen, 0}, c.list1, nullptr, h->stream.get()))) return rc;
+    if (!p.drain && (rc = intra_tail(c, h->stream.get()))) return rc;
     return inter_tail(c);
 }
 
@@ -1779,19 +1757,19 @@ int deferred_tails(Scan& c) {
     sw_handle* h = c.h;
     int rc;
     if (!c.deferred || !(c.inter_tail || c.intra_tail)) return SW_OK;
-    const RescueStages s = rescue_stages(c, c.x, tail_rows(c.db), false);
+    const RescueStages s = rescue_stages(c, c.x, tail_rows(c.db->lay), false);
     if (c.inter_tail) {
-        HIPCHECK(hipStreamWaitEvent(h->tail, h->main_done, 0));
-        if ((rc = launch_inter_tail(c, h->tail, s))) return rc;
+        HIPCHECK(hipStreamWaitEvent(h->tail.get(), h->main_done.get(), 0));
+        if ((rc = launch_inter_tail(c, h->tail.get(), s))) return rc;
     }
     if (c.intra_tail) {
-        HIPCHECK(hipStreamWaitEvent(h->tail, h->side_done, 0));
-        if ((rc = launch_intra_tail(c, h->tail, s))) return rc;
+        HIPCHECK(hipStreamWaitEvent(h->tail.get(), h->side_done.get(), 0));
+        if ((rc = launch_intra_tail(c, h->tail.get(), s))) return rc;
     }
-    HIPCHECK(hipEventRecord(h->tail_done[c.par], h->tail));
+    HIPCHECK(hipEventRecord(h->tail_done[c.par].get(), h->tail.get()));
     h->tail_pending[c.par] = true;
     sw_handle::ProfSlot& S = h->prof[c.P.slot];
-    HIPCHECK(hipEventRecord(S.tail_read, h->tail));
+    HIPCHECK(hipEventRecord(S.tail_read.get(), h->tail.get()));
     S.tail_pending = true;
     return SW_OK;
 }
@@ -1800,8 +1778,8 @@ int deferred_tails(Scan& c) {
 int print_rescue_stats(const Scan& c) {
     sw_handle* h = c.h;
     const sw_db* db = c.db;
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    HIPCHECK(hipStreamSynchronize(h->tail));
+    HIPCHECK(hipStreamSynchronize(h->stream.get()));
+    HIPCHECK(hipStreamSynchronize(h->tail.get()));
     int32_t cA = 0, cB = 0, l1 = 0, l2 = 0;
     std::vector<int32_t> ids;
     if (c.listA) {
@@ -1853,7 +1831,7 @@ int scan_impl_body(sw_handle* h, const sw_db* cdb, const QuerySrc& src, int32_t*
     if (src.pssm && (rc = check_pssm(h, src.pssm, go, ge))) return rc;
     if ((rc = check_fault(h))) return rc;
     if (!src.pssm && (rc = check_scoring(src.sc, &mat, &go, &ge))) return rc;
-    if (!db->built && (rc = build_db(db))) return rc;
+    if (!db->lay.built && (rc = build_db(db))) return rc;
     HIPCHECK(hipSetDevice(h->device));
     h->launches = 0;
     h->had_intra = false;
@@ -1905,9 +1883,9 @@ int scan_impl_body(sw_handle* h, const sw_db* cdb, const QuerySrc& src, int32_t*
     } else {
         // fork: the side streams start when the main stream reaches ev[0]
         // (the merged launch has none: its scan time runs from ev[6])
-        MARK(0, h->stream);
+        MARK(0, h->stream.get());
         if (db->nlong && (rc = long_pass(c))) return rc;
-        MARK(1, db->nlong ? h->side : h->stream);
+        MARK(1, db->nlong ? h->side.get() : h->stream.get());
         if (db->nblocks && (rc = inter_pass(c))) return rc;
     }
     if ((rc = deferred_tails(c))) return rc;
@@ -1915,13 +1893,13 @@ int scan_impl_body(sw_handle* h, const sw_db* cdb, const QuerySrc& src, int32_t*
     // join (the merged launch has no separate inter end, nor a side stream
     // to join), rank, and the end event
     if (!db->nblocks)
-        for (int k = 6; k < 8; ++k) MARK(k, h->stream);
-    if (!p.lpt) MARK(2, h->stream);
-    if (db->nlong && !p.lpt) HIPCHECK(hipStreamWaitEvent(h->stream, h->ev[1], 0));
+        for (int k = 6; k < 8; ++k) MARK(k, h->stream.get());
+    if (!p.lpt) MARK(2, h->stream.get());
+    if (db->nlong && !p.lpt) HIPCHECK(hipStreamWaitEvent(h->stream.get(), h->ev[1].get(), 0));
     // the scan completes on the handle's stream: so do earlier deferred tails
     if (!c.deferred && (rc = join_tails(h))) return rc;
     if (rq && (rc = rank_after(h, db, scores_dev, *rq))) return rc;
-    MARK(3, h->stream);
+    MARK(3, h->stream.get());
     h->open_slot = -1;
     h->evpool[h->nscans - 1].launches = h->launches;
     h->timed = true;
@@ -1936,8 +1914,7 @@ int scan_impl(sw_handle* h, const sw_db* db, const QuerySrc& src, int32_t* score
               const RankReq* rq = nullptr) {
     const int rc = scan_impl_body(h, db, src, scores_dev, defer, rq);
     if (h && h->open_slot >= 0) {
-        for (hipStream_t st : {h->stream, h->side, h->side2, h->tail})
-            if (st) (void)hipStreamSynchronize(st);
+        (void)quiesce(h);
         h->prof[h->open_slot].pending = false;
         h->open_slot = -1;
     }
@@ -1951,9 +1928,10 @@ int scan_impl(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen,
 
 int ensure_scores(sw_handle* h, size_t n) {
     if (n > h->scores_cap) {
-        if (h->d_scores) HIPCHECK(hipFree(h->d_scores));
-        h->scores_cap = std::max<size_t>(n, 1024);
-        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&h->d_scores), h->scores_cap * 4));
+        h->scores_cap = 0;
+        const size_t cap = std::max<size_t>(n, 1024);
+        HIPCHECK(swk::dev_alloc(h->d_scores, cap * 4));  // the old one released first: ~1 GiB (sw_scan_batch)
+        h->scores_cap = cap;
     }
     return SW_OK;
 }
@@ -1967,10 +1945,10 @@ int scan_host(sw_handle* h, const sw_db* db, const QuerySrc& src, int32_t* score
     HIPCHECK(hipSetDevice(h->device));
     if ((rc = ensure_scores(h, n))) return rc;
     // slots that no subject maps to read 0
-    HIPCHECK(hipMemsetAsync(h->d_scores, 0, n * 4, h->stream));
-    if ((rc = scan_impl(h, db, src, h->d_scores))) return rc;
-    HIPCHECK(hipMemcpyAsync(scores_host, h->d_scores, n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipMemsetAsync(h->d_scores.get(), 0, n * 4, h->stream.get()));
+    if ((rc = scan_impl(h, db, src, h->d_scores.get()))) return rc;
+    HIPCHECK(hipMemcpyAsync(scores_host, h->d_scores.get(), n * 4, hipMemcpyDeviceToHost, h->stream.get()));
+    HIPCHECK(hipStreamSynchronize(h->stream.get()));
     return check_fault(h);
 }
 
@@ -1986,13 +1964,13 @@ int scan_topk_host(sw_handle* h, const sw_db* cdb, const QuerySrc& src, int32_t 
     HIPCHECK(hipSetDevice(h->device));
     const size_t slots = static_cast<size_t>(db->max_id + 1);
     if ((rc = ensure_scores(h, slots + static_cast<size_t>(2 * k) + 2))) return rc;  // scores, then the k keys
-    int64_t* keys_dev = reinterpret_cast<int64_t*>(h->d_scores + round_up(static_cast<int64_t>(slots), 2));
+    int64_t* keys_dev = reinterpret_cast<int64_t*>(h->d_scores.get() + round_up(static_cast<int64_t>(slots), 2));
     // the ranking runs over the result ids of the subjects (rank_src)
     const RankReq rq{k, nullptr, 0, keys_dev};
-    if ((rc = scan_impl(h, db, src, h->d_scores, false, &rq))) return rc;
+    if ((rc = scan_impl(h, db, src, h->d_scores.get(), false, &rq))) return rc;
     HIPCHECK(hipMemcpyAsync(keys_host, keys_dev, static_cast<size_t>(k) * sizeof(int64_t), hipMemcpyDeviceToHost,
-                            h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
+                            h->stream.get()));
+    HIPCHECK(hipStreamSynchronize(h->stream.get()));
     return check_fault(h);
 }
 
@@ -2013,7 +1991,7 @@ int topk_impl(sw_handle* h, const int32_t* scores, const int64_t* keys, int64_t 
     src.keys = keys;
     src.gid = ids;
     src.id_base = id_base;
-    HIPCHECK(swk::launch_topk(src, n, k, out, h->d_topk_work, h->stream));
+    HIPCHECK(swk::launch_topk(src, n, k, out, h->d_topk_work.get(), h->stream.get()));
     return SW_OK;
 }
 }  // namespace
@@ -2065,14 +2043,13 @@ int sw_create(int32_t device, sw_handle** out) {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SW_E_NODEVICE, "no HIP device visible");
     if (device < 0 || device >= ndev) return fail(SW_E_INVALID, "device index out of range");
     HIPCHECK(hipSetDevice(device));
-    auto* h = new (std::nothrow) sw_handle();
+    std::unique_ptr<sw_handle> h(new (std::nothrow) sw_handle());
     if (!h) return fail(SW_E_NOMEM, "out of host memory");
     h->device = device;
     // the device's CUs, once (the merged launch's slot counts: lpt_tail_blocks,
     // the looped grid's size)
     if (hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) h->cus = 0;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete h; return fail(SW_E_HIP, hipGetErrorString(e)); }
+    HIPCHECK(swk::stream_create(h->stream, hipStreamNonBlocking));
     h->own_stream = true;
     // side and side2 are created with the handle, right after its own
     // stream: HIP maps normal-priority streams onto GPU_MAX_HW_QUEUES (4)
@@ -2081,71 +2058,36 @@ int sw_create(int32_t device, sw_handle** out) {
     // Created on first use instead, side2 shared the caller's queue
     // and the int16 launch beside the fp16 one ran after it (C3 under the
     // reference scoring 12,840 -> 8,900 GCUPS).
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->side2, hipStreamNonBlocking);
+    HIPCHECK(swk::stream_create(h->side, hipStreamNonBlocking));
+    HIPCHECK(swk::stream_create(h->side2, hipStreamNonBlocking));
     // The deferred rescue tails (batches) run at high priority: HIP serves
     // those streams from a separate queue pool, so a tail never shares a
     // hardware queue with the next query's scan (sharing one, the next
     // scan waited behind the tail: C3, the reference scoring's long queries
     // stalled 9-13 ms each behind their int16 list kernel).
-    if (e == hipSuccess) {
-        int least = 0, greatest = 0;
-        e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-        if (e == hipSuccess) e = hipStreamCreateWithPriority(&h->tail, hipStreamNonBlocking, greatest);
-    }
-    for (hipEvent_t* ev : {&h->main_done, &h->side_done, &h->tail_done[0], &h->tail_done[1]})
-        if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
-    for (auto& S : h->prof) {
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&S.tail_read, hipEventDisableTiming);
-    }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->coop_done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->fork2, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->h_fault), sizeof(int32_t), hipHostMallocMapped);
-    if (e == hipSuccess) {
-        *h->h_fault = 0;
-        e = hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_fault), h->h_fault, 0);
-    }
-    for (auto& ev : h->stage_ev)
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e != hipSuccess) { delete h; return fail(SW_E_HIP, hipGetErrorString(e)); }
-    *out = h;
+    int least = 0, greatest = 0;
+    HIPCHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    HIPCHECK(swk::stream_create(h->tail, hipStreamNonBlocking, greatest));
+    for (Event* ev : {&h->main_done, &h->side_done, &h->tail_done[0], &h->tail_done[1], &h->coop_done, &h->fork2,
+                      &h->stage_ev[0], &h->stage_ev[1]})
+        HIPCHECK(swk::event_create(*ev, hipEventDisableTiming));
+    for (auto& S : h->prof) HIPCHECK(swk::event_create(S.tail_read, hipEventDisableTiming));
+    HIPCHECK(swk::host_alloc(h->h_fault, sizeof(int32_t), hipHostMallocMapped));
+    *h->h_fault.get() = 0;
+    HIPCHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_fault), h->h_fault.get(), 0));
+    *out = h.release();
     return SW_OK;
 }
 
 int sw_destroy(sw_handle* h) {
     if (!h) return SW_OK;
     (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (auto& se : h->evpool)
-        for (auto& ev : se.ev)
-            if (ev) (void)hipEventDestroy(ev);
-    if (h->side) (void)hipStreamSynchronize(h->side);
-    if (h->side2) (void)hipStreamSynchronize(h->side2);
-    if (h->tail) (void)hipStreamSynchronize(h->tail);
-    for (auto& S : h->prof) {
-        if (S.d) (void)hipFree(S.d);
-        if (S.tail_read) (void)hipEventDestroy(S.tail_read);
-    }
-    if (h->d_scores) (void)hipFree(h->d_scores);
-    if (h->d_topk_work) (void)hipFree(h->d_topk_work);
-    for (int b = 0; b < 2; ++b) {
-        if (h->stage[b]) (void)hipHostFree(h->stage[b]);
-        if (h->stage_ev[b]) (void)hipEventDestroy(h->stage_ev[b]);
-    }
-    if (h->side) (void)hipStreamDestroy(h->side);
-    if (h->side2) (void)hipStreamDestroy(h->side2);
-    if (h->tail) (void)hipStreamDestroy(h->tail);
-    for (hipEvent_t ev : {h->main_done, h->side_done, h->tail_done[0], h->tail_done[1]})
-        if (ev) (void)hipEventDestroy(ev);
-    if (h->coop_done) (void)hipEventDestroy(h->coop_done);
-    if (h->fork2) (void)hipEventDestroy(h->fork2);
-    if (h->h_fault) (void)hipHostFree(h->h_fault);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    (void)quiesce(h);
     delete h;
     return SW_OK;
 }
 
-void* sw_stream(sw_handle* h) { return h ? reinterpret_cast<void*>(h->stream) : nullptr; }
+void* sw_stream(sw_handle* h) { return h ? reinterpret_cast<void*>(h->stream.get()) : nullptr; }
 
 int sw_opts_init(sw_opts* o) {
     if (!o) return fail(SW_E_INVALID, "null argument");
@@ -2208,13 +2150,13 @@ int sw_get_opts(const sw_handle* h, sw_opts* o) {
 
 int sw_set_stream(sw_handle* h, void* hip_stream) {
     if (!h) return fail(SW_E_INVALID, "null handle");
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    if (h->own_stream) HIPCHECK(hipStreamDestroy(h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream.get()));
+    if (!h->own_stream) h->stream.release();  // the caller's
+    h->own_stream = false;
     if (hip_stream) {
-        h->stream = reinterpret_cast<hipStream_t>(hip_stream);
-        h->own_stream = false;
+        h->stream = Stream(reinterpret_cast<hipStream_t>(hip_stream));  // borrowed (~sw_handle)
     } else {
-        HIPCHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+        HIPCHECK(swk::stream_create(h->stream, hipStreamNonBlocking));
         h->own_stream = true;
     }
     return SW_OK;
@@ -2231,7 +2173,7 @@ int sw_db_create(sw_handle* h, const uint8_t* residues, const int64_t* offsets, 
     if (total > 0 && !residues) return fail(SW_E_INVALID, "null residues");
     for (int64_t k = 0; k < n; ++k)
         if (offsets[k + 1] - offsets[k] > (int64_t(1) << 30)) return fail(SW_E_INVALID, "subject too long");
-    auto* db = new (std::nothrow) sw_db();
+    std::unique_ptr<sw_db> db(new (std::nothrow) sw_db());
     if (!db) return fail(SW_E_NOMEM, "out of host memory");
     db->h = h;
     db->n = n;
@@ -2242,7 +2184,6 @@ int sw_db_create(sw_handle* h, const uint8_t* residues, const int64_t* offsets, 
         db->h_ids.resize(n);
         for (int64_t k = 0; k < n; ++k) db->h_ids[k] = ids ? ids[k] : static_cast<int32_t>(k);
     } catch (...) {
-        delete db;
         return fail(SW_E_NOMEM, "out of host memory");
     }
     // copy and validate in parallel 1 MiB pieces
@@ -2255,21 +2196,17 @@ int sw_db_create(sw_handle* h, const uint8_t* residues, const int64_t* offsets, 
         for (int64_t k = lo; k < hi; ++k) m = std::max(m, residues[k]);
         if (m >= SW_ALPHABET) bad = true;
     }, 1);
-    if (bad) {
-        delete db;
-        return fail(SW_E_INVALID, "residue code out of range (use sw_encode)");
-    }
+    if (bad) return fail(SW_E_INVALID, "residue code out of range (use sw_encode)");
     db->residues = total;
     for (int64_t k = 0; k < n; ++k) {
         db->max_len = std::max<int32_t>(db->max_len, static_cast<int32_t>(offsets[k + 1] - offsets[k]));
-        if (db->h_ids[k] < 0) { delete db; return fail(SW_E_INVALID, "ids must be >= 0"); }
+        if (db->h_ids[k] < 0) return fail(SW_E_INVALID, "ids must be >= 0");
         db->max_id = std::max(db->max_id, db->h_ids[k]);
     }
-    db->long_threshold = swplan::default_long_threshold(plan_view(db));
+    db->long_threshold = swplan::default_long_threshold(plan_view(db.get()));
     HIPCHECK(hipSetDevice(h->device));
-    int rc = build_db(db);
-    if (rc) { free_dev(db); delete db; return rc; }
-    *out = db;
+    if (int rc = build_db(db.get())) return rc;
+    *out = db.release();
     return SW_OK;
 }
 
@@ -2380,7 +2317,7 @@ int sw_synth_lengths(uint64_t seed, int64_t id_base, int64_t n, int32_t* lengths
 int sw_db_create_synthetic(sw_handle* h, uint64_t seed, int64_t id_base, int64_t n, sw_db** out) {
     if (!h || !out || n < 0 || id_base < 0 || n > (int64_t(1) << 31) - 1) return fail(SW_E_INVALID, "bad argument");
     *out = nullptr;
-    auto* db = new (std::nothrow) sw_db();
+    std::unique_ptr<sw_db> db(new (std::nothrow) sw_db());
     if (!db) return fail(SW_E_NOMEM, "out of host memory");
     db->h = h;
     db->n = n;
@@ -2396,16 +2333,14 @@ int sw_db_create_synthetic(sw_handle* h, uint64_t seed, int64_t id_base, int64_t
         for (int64_t k = 0; k < n; ++k) db->h_ids[k] = static_cast<int32_t>(k);
         for (int64_t k = 0; k < n; ++k) db->max_len = std::max(db->max_len, L[k]);
     } catch (...) {
-        delete db;
         return fail(SW_E_NOMEM, "out of host memory");
     }
     db->residues = db->h_offsets[n];
     db->max_id = static_cast<int32_t>(n - 1);
-    db->long_threshold = swplan::default_long_threshold(plan_view(db));
+    db->long_threshold = swplan::default_long_threshold(plan_view(db.get()));
     HIPCHECK(hipSetDevice(h->device));
-    int rc = build_db(db);
-    if (rc) { free_dev(db); delete db; return rc; }
-    *out = db;
+    if (int rc = build_db(db.get())) return rc;
+    *out = db.release();
     return SW_OK;
 }
 
@@ -2421,29 +2356,21 @@ int sw_db_subjects(const sw_db* db, int64_t* lengths, int32_t* ids) {
 int sw_db_free(sw_db* db) {
     if (!db) return SW_OK;
     (void)hipSetDevice(db->h->device);
-    (void)hipStreamSynchronize(db->h->stream);
-    if (db->h->side) (void)hipStreamSynchronize(db->h->side);
-    if (db->h->tail) (void)hipStreamSynchronize(db->h->tail);
-    if (db->h_trace) {  // the last scan's block timeline (tail analysis builds)
+    (void)quiesce(db->h);
+    if (db->lay.h_trace.get()) {  // the last scan's block timeline (tail analysis builds)
         if (const char* path = db->h->opts.trace_file; path[0])
             if (FILE* f = std::fopen(path, "wb")) {
-                std::fwrite(db->h_trace, 32, db->trace_entries, f);
+                std::fwrite(db->lay.h_trace.get(), 32, db->lay.trace_entries, f);
                 std::fclose(f);
             }
     }
-    readback_free(db->lcount);
-    readback_free(db->icount);
-    free_dev(db);
     delete db;
     return SW_OK;
 }
 
 int sw_db_reset_adaptive(sw_db* db) {
     if (!db) return fail(SW_E_INVALID, "null argument");
-    readback_reset(db->lcount);
-    db->i16_first.clear();
-    readback_reset(db->icount);
-    db->i16_span.clear();
+    reset_adaptive(db);
     return SW_OK;
 }
 
@@ -2454,14 +2381,14 @@ int sw_db_get_stats(const sw_db* db, sw_db_stats* out) {
     out->packed_cells = db->packed_cells;
     out->n_blocks = db->nblocks;
     out->n_long = db->nlong;
-    out->device_bytes = static_cast<int64_t>(db->device_bytes);
+    out->device_bytes = static_cast<int64_t>(db->lay.device_bytes);
     out->max_length = db->max_len;
     out->long_threshold = db->long_threshold;
-    out->coop_blocks = db->built ? db->last_ncoop : 0;
+    out->coop_blocks = db->lay.built ? db->last_ncoop : 0;
     out->coop_residues = 0;
     for (int32_t b = 0; b < out->coop_blocks; ++b) out->coop_residues += db->h_blk_res[b];
-    out->pair_blocks = db->built ? db->last_npair : 0;
-    out->pair_merged = db->built && db->last_pair_merged ? 1 : 0;
+    out->pair_blocks = db->lay.built ? db->last_npair : 0;
+    out->pair_merged = db->lay.built && db->last_pair_merged ? 1 : 0;
     out->pair_residues = 0;
     for (int32_t b = 0; b < out->pair_blocks; ++b) out->pair_residues += db->h_blk_res[b];
     out->max_id = db->max_id;
@@ -2472,11 +2399,9 @@ int sw_db_set_long_threshold(sw_db* db, int32_t threshold) {
     if (!db) return fail(SW_E_INVALID, "null argument");
     if (threshold < 0) return fail(SW_E_INVALID, "threshold must be >= 0");
     const int32_t t = threshold == 0 ? swplan::default_long_threshold(plan_view(db)) : threshold;
-    if (t == db->long_threshold && db->built) return SW_OK;
+    if (t == db->long_threshold && db->lay.built) return SW_OK;
     HIPCHECK(hipSetDevice(db->h->device));
-    HIPCHECK(hipStreamSynchronize(db->h->stream));
-    if (db->h->side) HIPCHECK(hipStreamSynchronize(db->h->side));
-    if (db->h->tail) HIPCHECK(hipStreamSynchronize(db->h->tail));
+    HIPCHECK(quiesce(db->h));
     free_dev(db);
     db->long_threshold = t;
     return build_db(db);
@@ -2515,12 +2440,8 @@ int sw_pssm_create(sw_handle* h, const int8_t* rows, int32_t qlen, sw_pssm** out
             p->image[static_cast<size_t>(c) * p->ld + i] = v;
         }
     HIPCHECK(hipSetDevice(h->device));
-    HIPCHECK(hipMalloc(reinterpret_cast<void**>(&p->d), p->image.size()));
-    const hipError_t e = hipMemcpyAsync(p->d, p->image.data(), p->image.size(), hipMemcpyHostToDevice, h->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(p->d);
-        return fail(SW_E_HIP, hipGetErrorString(e));
-    }
+    HIPCHECK(swk::dev_alloc(p->d, p->image.size()));
+    HIPCHECK(hipMemcpyAsync(p->d.get(), p->image.data(), p->image.size(), hipMemcpyHostToDevice, h->stream.get()));
     *out = p.release();
     return SW_OK;
 }
@@ -2529,10 +2450,7 @@ int sw_pssm_free(sw_pssm* p) {
     if (!p) return SW_OK;
     // scans in flight on the handle may still read the table
     (void)hipSetDevice(p->h->device);
-    (void)hipStreamSynchronize(p->h->stream);
-    if (p->h->side) (void)hipStreamSynchronize(p->h->side);
-    if (p->h->tail) (void)hipStreamSynchronize(p->h->tail);
-    if (p->d) (void)hipFree(p->d);
+    (void)quiesce(p->h);
     delete p;
     return SW_OK;
 }
@@ -2610,10 +2528,11 @@ int sw_scan_batch(sw_handle* h, const sw_db* db, const uint8_t* queries, const i
     if ((rc = ensure_scores(h, chunk * n))) return rc;
     for (int32_t k0 = 0; k0 < nq; k0 += chunk) {
         const int32_t m = std::min(chunk, nq - k0);
-        HIPCHECK(hipMemsetAsync(h->d_scores, 0, m * n * 4, h->stream));  // unmapped slots read 0
-        if ((rc = sw_scan_batch_device(h, db, queries, qoffsets + k0, m, sc, h->d_scores))) return rc;
-        HIPCHECK(hipMemcpyAsync(scores_host + k0 * n, h->d_scores, m * n * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHECK(hipStreamSynchronize(h->stream));
+        HIPCHECK(hipMemsetAsync(h->d_scores.get(), 0, m * n * 4, h->stream.get()));  // unmapped slots read 0
+        if ((rc = sw_scan_batch_device(h, db, queries, qoffsets + k0, m, sc, h->d_scores.get()))) return rc;
+        HIPCHECK(hipMemcpyAsync(scores_host + k0 * n, h->d_scores.get(), m * n * 4, hipMemcpyDeviceToHost,
+                                h->stream.get()));
+        HIPCHECK(hipStreamSynchronize(h->stream.get()));
         if ((rc = check_fault(h))) return rc;
     }
     return SW_OK;
@@ -2621,23 +2540,23 @@ int sw_scan_batch(sw_handle* h, const sw_db* db, const uint8_t* queries, const i
 
 namespace {
 int read_events(const ScanEvents& se, sw_timing* t) {
-    HIPCHECK(hipEventSynchronize(se.ev[3]));
+    HIPCHECK(hipEventSynchronize(se.ev[3].get()));
     // intra runs on the side stream from the fork (ev0) to ev1; inter on the
     // main stream from ev0 to ev2; they overlap.
     // (events a scan did not record: the intra and inter spans fall back to
     // the whole scan, the cooperative kernel's to 0; a scan without a fork,
     // the merged launch, starts at ev6)
     auto has = [&](int k) { return (se.rec >> k & 1u) != 0; };
-    const hipEvent_t start = has(0) ? se.ev[0] : se.ev[6];
+    const hipEvent_t start = has(0) ? se.ev[0].get() : se.ev[6].get();
     float t01 = 0, t02 = 0, t03 = 0;
-    HIPCHECK(hipEventElapsedTime(&t03, start, se.ev[3]));
+    HIPCHECK(hipEventElapsedTime(&t03, start, se.ev[3].get()));
     t01 = t02 = t03;
-    if (has(1)) HIPCHECK(hipEventElapsedTime(&t01, start, se.ev[1]));
-    if (has(2)) HIPCHECK(hipEventElapsedTime(&t02, start, se.ev[2]));
+    if (has(1)) HIPCHECK(hipEventElapsedTime(&t01, start, se.ev[1].get()));
+    if (has(2)) HIPCHECK(hipEventElapsedTime(&t02, start, se.ev[2].get()));
     float t45 = 0, t67 = 0;
-    if (has(4) && has(5)) HIPCHECK(hipEventElapsedTime(&t45, se.ev[4], se.ev[5]));
+    if (has(4) && has(5)) HIPCHECK(hipEventElapsedTime(&t45, se.ev[4].get(), se.ev[5].get()));
     // (a merged launch that drains its own rescue lists ends the scan: ev[3])
-    if (has(6)) HIPCHECK(hipEventElapsedTime(&t67, se.ev[6], has(7) ? se.ev[7] : se.ev[3]));
+    if (has(6)) HIPCHECK(hipEventElapsedTime(&t67, se.ev[6].get(), has(7) ? se.ev[7].get() : se.ev[3].get()));
     if (se.merged) {  // the merged launch: no separate intra span
         t01 = 0;
         t02 = t67;
@@ -2665,7 +2584,7 @@ int sw_stream_wait_scan(sw_handle* h, void* hip_stream) {
     if ((rc = check_fault(h))) return rc;  // (a completed earlier scan's fault)
     if (!h->timed || h->nscans == 0) return SW_OK;  // no scan yet: nothing to wait for
     HIPCHECK(hipSetDevice(h->device));
-    HIPCHECK(hipStreamWaitEvent(reinterpret_cast<hipStream_t>(hip_stream), h->evpool[h->nscans - 1].ev[3], 0));
+    HIPCHECK(hipStreamWaitEvent(reinterpret_cast<hipStream_t>(hip_stream), h->evpool[h->nscans - 1].ev[3].get(), 0));
     return SW_OK;
 }
 
@@ -2795,64 +2714,52 @@ int align_impl(sw_handle* h, const sw_db* cdb, const QuerySrc& src, const int32_
             hdoff[k] = dacc;
             dacc += (qlen + L + 1) * W1;
         }
-        uint8_t *dq = nullptr, *dsub = nullptr, *ddir = nullptr;
-        int64_t *doff = nullptr, *ddoff = nullptr;
-        int8_t* dmat = nullptr;
-        int32_t *dh = nullptr, *dout = nullptr;
-        char* dops = nullptr;
-        auto cleanup = [&]() {
-            void* ptrs[] = {dq, dsub, ddir, doff, ddoff, dmat, dh, dout, dops};
-            for (void* p : ptrs)
-                if (p) (void)hipFree(p);
-        };
-        hipError_t e = hipSuccess;
-        auto alloc = [&](auto** p, size_t b) {
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(b, 1));
-        };
-        if (!src.pssm) alloc(&dq, qlen);
-        alloc(&dsub, hsub.size());
-        alloc(&doff, (m + 1) * sizeof(int64_t));
-        alloc(&ddoff, m * sizeof(int64_t));
-        if (!src.pssm) alloc(&dmat, 625);
-        alloc(&ddir, static_cast<size_t>(dacc));
-        // H: three diagonals; affine also two of E and two of F
-        alloc(&dh, static_cast<size_t>(m) * (go != ge ? 7 : 3) * W1 * sizeof(int32_t));
-        alloc(&dout, static_cast<size_t>(m) * 6 * sizeof(int32_t));
-        if (ops) alloc(&dops, static_cast<size_t>(m) * ops_stride);
-        if (e == hipSuccess && !src.pssm) e = hipMemcpyAsync(dq, query, qlen, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dsub, hsub.data(), hsub.size(), hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(doff, hoff.data(), (m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ddoff, hdoff.data(), m * sizeof(int64_t), hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess && !src.pssm) e = hipMemcpyAsync(dmat, mat, 625, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) {
-            swk::AlignArgs a{};
-            a.query = dq;
-            a.qlen = qlen;
-            a.subj = dsub;
-            a.subj_off = doff;
-            a.n = m;
-            a.mat = dmat;
-            a.pssm = src.pssm ? src.pssm->d : nullptr;
-            a.pssm_ld = src.pssm ? src.pssm->ld : 0;
-            a.gap = go;
-            a.gap_extend = ge;
-            a.dirs = ddir;
-            a.dirs_off = ddoff;
-            a.hbuf = dh;
-            a.out = dout;
-            a.ops = dops;
-            a.ops_stride = ops ? ops_stride : 0;
-            e = swk::launch_align(a, h->stream);
-        }
         std::vector<int32_t> hout(static_cast<size_t>(m) * 6);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(hout.data(), dout, hout.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess && ops)
-            e = hipMemcpyAsync(ops + static_cast<int64_t>(k0) * ops_stride, dops, static_cast<size_t>(m) * ops_stride,
-                               hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        cleanup();
-        if (e != hipSuccess) return fail(SW_E_HIP, hipGetErrorString(e));
+        // this group's buffers (qlen, m >= 1: no empty one), released after the synchronise below
+        DevPtr<uint8_t> dq, dsub, ddir;
+        DevPtr<int64_t> doff, ddoff;
+        DevPtr<int8_t> dmat;
+        DevPtr<int32_t> dh, dout;
+        DevPtr<char> dops;
+        if (!src.pssm) HIPCHECK(swk::dev_alloc(dq, qlen));
+        HIPCHECK(swk::dev_alloc(dsub, hsub.size()));
+        HIPCHECK(swk::dev_alloc(doff, (m + 1) * sizeof(int64_t)));
+        HIPCHECK(swk::dev_alloc(ddoff, m * sizeof(int64_t)));
+        if (!src.pssm) HIPCHECK(swk::dev_alloc(dmat, 625));
+        HIPCHECK(swk::dev_alloc(ddir, static_cast<size_t>(dacc)));
+        // H: three diagonals; affine also two of E and two of F
+        HIPCHECK(swk::dev_alloc(dh, static_cast<size_t>(m) * (go != ge ? 7 : 3) * W1 * sizeof(int32_t)));
+        HIPCHECK(swk::dev_alloc(dout, static_cast<size_t>(m) * 6 * sizeof(int32_t)));
+        if (ops) HIPCHECK(swk::dev_alloc(dops, static_cast<size_t>(m) * ops_stride));
+        hipStream_t const s = h->stream.get();
+        if (!src.pssm) HIPCHECK(hipMemcpyAsync(dq.get(), query, qlen, hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(dsub.get(), hsub.data(), hsub.size(), hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(doff.get(), hoff.data(), (m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(ddoff.get(), hdoff.data(), m * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        if (!src.pssm) HIPCHECK(hipMemcpyAsync(dmat.get(), mat, 625, hipMemcpyHostToDevice, s));
+        swk::AlignArgs a{};
+        a.query = dq.get();
+        a.qlen = qlen;
+        a.subj = dsub.get();
+        a.subj_off = doff.get();
+        a.n = m;
+        a.mat = dmat.get();
+        a.pssm = src.pssm ? src.pssm->d.get() : nullptr;
+        a.pssm_ld = src.pssm ? src.pssm->ld : 0;
+        a.gap = go;
+        a.gap_extend = ge;
+        a.dirs = ddir.get();
+        a.dirs_off = ddoff.get();
+        a.hbuf = dh.get();
+        a.out = dout.get();
+        a.ops = dops.get();
+        a.ops_stride = ops ? ops_stride : 0;
+        HIPCHECK(swk::launch_align(a, s));
+        HIPCHECK(hipMemcpyAsync(hout.data(), dout.get(), hout.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (ops)
+            HIPCHECK(hipMemcpyAsync(ops + static_cast<int64_t>(k0) * ops_stride, dops.get(),
+                                    static_cast<size_t>(m) * ops_stride, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipStreamSynchronize(s));
         for (int32_t k = 0; k < m; ++k) {
             sw_alignment& o = out[k0 + k];
             if (slen_of(sidx[k0 + k]) == 0) continue;  // empty subject: all zero (as the oracle)

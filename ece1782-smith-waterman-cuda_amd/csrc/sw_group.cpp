@@ -26,7 +26,6 @@
 // which path ran and why.  A group of one device runs the RCCL path with a
 // one-rank communicator.
 #include <dlfcn.h>
-#include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -37,18 +36,12 @@
 #include <thread>
 #include <vector>
 
-#include "sw_amd.h"
-#include "sw_kernels.h"
+#include "sw_host.h"
+
+using swk::DevPtr;
+using swk::set_error;
 
 namespace {
-
-int gfail(int code, const std::string& msg) { return swk::set_error(code, msg); }
-
-#define GHIP(expr)                                                                        \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) return gfail(SW_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 struct Rccl {
     void* lib = nullptr;
@@ -100,7 +93,7 @@ int for_each_device(int n, const std::function<int(int)>& f) {
         });
     for (auto& t : th) t.join();
     for (int d = 0; d < n; ++d)
-        if (rc[d] != SW_OK) return gfail(rc[d], "device " + std::to_string(d) + ": " + err[d]);
+        if (rc[d] != SW_OK) return set_error(rc[d], "device " + std::to_string(d) + ": " + err[d]);
     return SW_OK;
 }
 
@@ -113,9 +106,9 @@ struct sw_group {
     bool distinct = false;          // every device listed once: RCCL possible
     bool comm_tried = false;        // communicators created (or failed) already
     // per device: K local keys, G x K gathered keys, capacity in keys
-    std::vector<int64_t*> d_keys, d_all;
+    std::vector<DevPtr<int64_t>> d_keys, d_all;
     int32_t kcap = 0;
-    int64_t* d_final = nullptr;  // merged keys on device 0
+    DevPtr<int64_t> d_final;  // merged keys on device 0
     std::string exchange = "none";
 };
 
@@ -123,8 +116,8 @@ struct sw_gdb {
     sw_group* g = nullptr;
     std::vector<sw_db*> db;
     std::vector<std::vector<int32_t>> ids;  // per shard: local k -> global result id
-    std::vector<int32_t*> d_ids;            // device copies (top-K id maps)
-    std::vector<int32_t*> d_scores;         // per device: local scores (device)
+    std::vector<DevPtr<int32_t>> d_ids;     // device copies (top-K id maps)
+    std::vector<DevPtr<int32_t>> d_scores;  // per device: local scores (device)
     int64_t n = 0;
     int32_t max_id = -1;
 };
@@ -134,16 +127,14 @@ namespace {
 int ensure_keys(sw_group* g, int32_t k) {
     if (k <= g->kcap) return SW_OK;
     const int n = static_cast<int>(g->devices.size());
+    g->kcap = 0;  // until every buffer holds k keys
     for (int d = 0; d < n; ++d) {
-        GHIP(hipSetDevice(g->devices[d]));
-        if (g->d_keys[d]) GHIP(hipFree(g->d_keys[d]));
-        if (g->d_all[d]) GHIP(hipFree(g->d_all[d]));
-        GHIP(hipMalloc(reinterpret_cast<void**>(&g->d_keys[d]), sizeof(int64_t) * k));
-        GHIP(hipMalloc(reinterpret_cast<void**>(&g->d_all[d]), sizeof(int64_t) * k * n));
+        HIPCHECK(hipSetDevice(g->devices[d]));
+        HIPCHECK(swk::dev_alloc(g->d_keys[d], sizeof(int64_t) * k));
+        HIPCHECK(swk::dev_alloc(g->d_all[d], sizeof(int64_t) * k * n));
     }
-    GHIP(hipSetDevice(g->devices[0]));
-    if (g->d_final) GHIP(hipFree(g->d_final));
-    GHIP(hipMalloc(reinterpret_cast<void**>(&g->d_final), sizeof(int64_t) * k));
+    HIPCHECK(hipSetDevice(g->devices[0]));
+    HIPCHECK(swk::dev_alloc(g->d_final, sizeof(int64_t) * k));
     g->kcap = k;
     return SW_OK;
 }
@@ -176,20 +167,20 @@ void ensure_comms(sw_group* g) {
 extern "C" {
 
 int sw_group_create(const int32_t* devices, int32_t ndev, sw_group** out) {
-    if (!out || ndev <= 0 || !devices) return gfail(SW_E_INVALID, "null argument / no devices");
+    if (!out || ndev <= 0 || !devices) return set_error(SW_E_INVALID, "null argument / no devices");
     *out = nullptr;
     auto* g = new (std::nothrow) sw_group();
-    if (!g) return gfail(SW_E_NOMEM, "out of host memory");
+    if (!g) return set_error(SW_E_NOMEM, "out of host memory");
     g->devices.assign(devices, devices + ndev);
     g->h.assign(ndev, nullptr);
-    g->d_keys.assign(ndev, nullptr);
-    g->d_all.assign(ndev, nullptr);
+    g->d_keys.resize(ndev);
+    g->d_all.resize(ndev);
     for (int d = 0; d < ndev; ++d) {
         const int rc = sw_create(devices[d], &g->h[d]);
         if (rc) {
             const std::string e = sw_last_error();
             sw_group_destroy(g);
-            return gfail(rc, e);
+            return set_error(rc, e);
         }
     }
     std::vector<int32_t> sorted(g->devices);
@@ -207,9 +198,9 @@ int sw_group_destroy(sw_group* g) {
         if (c) rccl().destroy(c);
     for (size_t d = 0; d < g->devices.size(); ++d) {
         (void)hipSetDevice(g->devices[d]);
-        if (g->d_keys[d]) (void)hipFree(g->d_keys[d]);
-        if (g->d_all[d]) (void)hipFree(g->d_all[d]);
-        if (d == 0 && g->d_final) (void)hipFree(g->d_final);
+        g->d_keys[d].reset();
+        g->d_all[d].reset();
+        if (d == 0) g->d_final.reset();
         if (g->h[d]) sw_destroy(g->h[d]);
     }
     delete g;
@@ -219,24 +210,24 @@ int sw_group_destroy(sw_group* g) {
 const char* sw_group_info(const sw_group* g) { return g ? g->exchange.c_str() : ""; }
 
 int sw_group_handle(sw_group* g, int32_t d, sw_handle** out) {
-    if (!g || !out || d < 0 || d >= static_cast<int32_t>(g->h.size())) return gfail(SW_E_INVALID, "bad device slot");
+    if (!g || !out || d < 0 || d >= static_cast<int32_t>(g->h.size())) return set_error(SW_E_INVALID, "bad device slot");
     *out = g->h[d];
     return SW_OK;
 }
 
 int sw_group_db_create(sw_group* g, const uint8_t* residues, const int64_t* offsets, int64_t n, const int32_t* ids,
                        sw_gdb** out) {
-    if (!g || !out || n < 0 || (n > 0 && !offsets)) return gfail(SW_E_INVALID, "null argument");
+    if (!g || !out || n < 0 || (n > 0 && !offsets)) return set_error(SW_E_INVALID, "null argument");
     *out = nullptr;
     const int G = static_cast<int>(g->devices.size());
     auto* gd = new (std::nothrow) sw_gdb();
-    if (!gd) return gfail(SW_E_NOMEM, "out of host memory");
+    if (!gd) return set_error(SW_E_NOMEM, "out of host memory");
     gd->g = g;
     gd->n = n;
     gd->db.assign(G, nullptr);
     gd->ids.assign(G, {});
-    gd->d_ids.assign(G, nullptr);
-    gd->d_scores.assign(G, nullptr);
+    gd->d_ids.resize(G);
+    gd->d_scores.resize(G);
     // LPT deal: longest first, each to the lightest shard (lowest index on ties)
     std::vector<int64_t> order(n);
     for (int64_t k = 0; k < n; ++k) order[k] = k;
@@ -260,7 +251,7 @@ int sw_group_db_create(sw_group* g, const uint8_t* residues, const int64_t* offs
         const int32_t id = ids ? ids[k] : static_cast<int32_t>(k);
         if (id < 0) {
             sw_group_db_free(gd);
-            return gfail(SW_E_INVALID, "ids must be >= 0");
+            return set_error(SW_E_INVALID, "ids must be >= 0");
         }
         gd->max_id = std::max(gd->max_id, id);
         gd->ids[d].push_back(id);
@@ -271,18 +262,18 @@ int sw_group_db_create(sw_group* g, const uint8_t* residues, const int64_t* offs
         const int64_t nd = static_cast<int64_t>(gd->ids[d].size());
         int r = sw_db_create(g->h[d], res[d].data(), offs[d].data(), nd, nullptr, &gd->db[d]);
         if (r) return r;
-        GHIP(hipSetDevice(g->devices[d]));
+        HIPCHECK(hipSetDevice(g->devices[d]));
         if (nd) {
-            GHIP(hipMalloc(reinterpret_cast<void**>(&gd->d_ids[d]), sizeof(int32_t) * nd));
-            GHIP(hipMalloc(reinterpret_cast<void**>(&gd->d_scores[d]), sizeof(int32_t) * nd));
-            GHIP(hipMemcpy(gd->d_ids[d], gd->ids[d].data(), sizeof(int32_t) * nd, hipMemcpyHostToDevice));
+            HIPCHECK(swk::dev_alloc(gd->d_ids[d], sizeof(int32_t) * nd));
+            HIPCHECK(swk::dev_alloc(gd->d_scores[d], sizeof(int32_t) * nd));
+            HIPCHECK(hipMemcpy(gd->d_ids[d].get(), gd->ids[d].data(), sizeof(int32_t) * nd, hipMemcpyHostToDevice));
         }
         return SW_OK;
     });
     if (rc) {
         const std::string e = sw_last_error();
         sw_group_db_free(gd);
-        return gfail(rc, e);
+        return set_error(rc, e);
     }
     *out = gd;
     return SW_OK;
@@ -293,15 +284,15 @@ int sw_group_db_free(sw_gdb* gd) {
     for (size_t d = 0; d < gd->db.size(); ++d) {
         (void)hipSetDevice(gd->g->devices[d]);
         if (gd->db[d]) sw_db_free(gd->db[d]);
-        if (gd->d_ids[d]) (void)hipFree(gd->d_ids[d]);
-        if (gd->d_scores[d]) (void)hipFree(gd->d_scores[d]);
+        gd->d_ids[d].reset();
+        gd->d_scores[d].reset();
     }
     delete gd;
     return SW_OK;
 }
 
 int sw_group_db_shard(const sw_gdb* gd, int32_t d, int64_t* n_subjects, int64_t* residues) {
-    if (!gd || d < 0 || d >= static_cast<int32_t>(gd->db.size())) return gfail(SW_E_INVALID, "bad shard");
+    if (!gd || d < 0 || d >= static_cast<int32_t>(gd->db.size())) return set_error(SW_E_INVALID, "bad shard");
     sw_db_stats st;
     const int rc = sw_db_get_stats(gd->db[d], &st);
     if (rc) return rc;
@@ -312,7 +303,7 @@ int sw_group_db_shard(const sw_gdb* gd, int32_t d, int64_t* n_subjects, int64_t*
 
 int sw_group_scan(sw_group* g, const sw_gdb* gd, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
                   int32_t* scores_host) {
-    if (!g || !gd || gd->g != g || (!scores_host && gd->n > 0)) return gfail(SW_E_INVALID, "null argument");
+    if (!g || !gd || gd->g != g || (!scores_host && gd->n > 0)) return set_error(SW_E_INVALID, "null argument");
     const int G = static_cast<int>(g->devices.size());
     if (gd->max_id >= 0) std::memset(scores_host, 0, sizeof(int32_t) * (static_cast<size_t>(gd->max_id) + 1));
     return for_each_device(G, [&](int d) {
@@ -329,7 +320,7 @@ int sw_group_scan(sw_group* g, const sw_gdb* gd, const uint8_t* query, int32_t q
 int sw_group_topk(sw_group* g, const sw_gdb* gd, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
                   int32_t k, int64_t* keys_host) {
     if (!g || !gd || gd->g != g || !keys_host || k <= 0 || k > 4096)
-        return gfail(SW_E_INVALID, "bad top-k arguments (1 <= k <= 4096)");
+        return set_error(SW_E_INVALID, "bad top-k arguments (1 <= k <= 4096)");
     const int G = static_cast<int>(g->devices.size());
     int rc = ensure_keys(g, k);
     if (rc) return rc;
@@ -337,9 +328,9 @@ int sw_group_topk(sw_group* g, const sw_gdb* gd, const uint8_t* query, int32_t q
     rc = for_each_device(G, [&](int d) {
         const int64_t nd = static_cast<int64_t>(gd->ids[d].size());
         if (nd)  // the shard's scores ranked with global ids, in the scan's launch when it is merged
-            return sw_scan_rank_device(g->h[d], gd->db[d], query, qlen, sc, gd->d_scores[d], k, gd->d_ids[d], 0,
-                                       g->d_keys[d]);
-        return sw_topk_device_ids(g->h[d], gd->d_scores[d], nd, gd->d_ids[d], k, g->d_keys[d]);
+            return sw_scan_rank_device(g->h[d], gd->db[d], query, qlen, sc, gd->d_scores[d].get(), k,
+                                       gd->d_ids[d].get(), 0, g->d_keys[d].get());
+        return sw_topk_device_ids(g->h[d], gd->d_scores[d].get(), nd, gd->d_ids[d].get(), k, g->d_keys[d].get());
     });
     if (rc) return rc;
     // 2. exchange: every device receives all G x k keys
@@ -347,30 +338,31 @@ int sw_group_topk(sw_group* g, const sw_gdb* gd, const uint8_t* query, int32_t q
     if (!g->comms.empty()) {
         ncclResult_t r = rccl().group_start();
         for (int d = 0; d < G && r == ncclSuccess; ++d) {
-            GHIP(hipSetDevice(g->devices[d]));
-            r = rccl().all_gather(g->d_keys[d], g->d_all[d], static_cast<size_t>(k), ncclInt64, g->comms[d],
-                                  static_cast<hipStream_t>(sw_stream(g->h[d])));
+            HIPCHECK(hipSetDevice(g->devices[d]));
+            r = rccl().all_gather(g->d_keys[d].get(), g->d_all[d].get(), static_cast<size_t>(k), ncclInt64,
+                                  g->comms[d], static_cast<hipStream_t>(sw_stream(g->h[d])));
         }
         const ncclResult_t e = rccl().group_end();
         if (r == ncclSuccess) r = e;
-        if (r != ncclSuccess) return gfail(SW_E_HIP, std::string("ncclAllGather: ") + rccl().error_string(r));
+        if (r != ncclSuccess) return set_error(SW_E_HIP, std::string("ncclAllGather: ") + rccl().error_string(r));
     } else {
         std::vector<int64_t> all(static_cast<size_t>(k) * G);
         for (int d = 0; d < G; ++d) {
-            GHIP(hipSetDevice(g->devices[d]));
-            GHIP(hipStreamSynchronize(static_cast<hipStream_t>(sw_stream(g->h[d]))));
-            GHIP(hipMemcpy(all.data() + static_cast<size_t>(k) * d, g->d_keys[d], sizeof(int64_t) * k,
+            HIPCHECK(hipSetDevice(g->devices[d]));
+            HIPCHECK(hipStreamSynchronize(static_cast<hipStream_t>(sw_stream(g->h[d]))));
+            HIPCHECK(hipMemcpy(all.data() + static_cast<size_t>(k) * d, g->d_keys[d].get(), sizeof(int64_t) * k,
                            hipMemcpyDeviceToHost));
         }
-        GHIP(hipSetDevice(g->devices[0]));
-        GHIP(hipMemcpy(g->d_all[0], all.data(), sizeof(int64_t) * all.size(), hipMemcpyHostToDevice));
+        HIPCHECK(hipSetDevice(g->devices[0]));
+        HIPCHECK(hipMemcpy(g->d_all[0].get(), all.data(), sizeof(int64_t) * all.size(), hipMemcpyHostToDevice));
     }
     // 3. device 0 merges (score desc, global id asc) and returns k keys
-    if ((rc = sw_topk_keys_device(g->h[0], g->d_all[0], static_cast<int64_t>(k) * G, k, g->d_final))) return rc;
-    GHIP(hipSetDevice(g->devices[0]));
+    rc = sw_topk_keys_device(g->h[0], g->d_all[0].get(), static_cast<int64_t>(k) * G, k, g->d_final.get());
+    if (rc) return rc;
+    HIPCHECK(hipSetDevice(g->devices[0]));
     hipStream_t s0 = static_cast<hipStream_t>(sw_stream(g->h[0]));
-    GHIP(hipMemcpyAsync(keys_host, g->d_final, sizeof(int64_t) * k, hipMemcpyDeviceToHost, s0));
-    GHIP(hipStreamSynchronize(s0));
+    HIPCHECK(hipMemcpyAsync(keys_host, g->d_final.get(), sizeof(int64_t) * k, hipMemcpyDeviceToHost, s0));
+    HIPCHECK(hipStreamSynchronize(s0));
     return SW_OK;
 }
 

@@ -76,6 +76,46 @@ def test_affine_vs_oracle(sw, oracle, handle, go, ge, mid):
     assert np.array_equal(got2, want)
 
 
+def test_rebuild_bookkeeping(sw, oracle, handle):
+    """sw_db_set_long_threshold releases one packed layout and builds the
+    next: every return to a threshold reports the device bytes, blocks and
+    long subjects of the first visit (the same calls made), a fresh database
+    at that threshold agrees, and every scan stays exact."""
+    r, o = sw.synth.database(400, shard=7)
+    q, q2 = sw.synth.query(250, shard=8), sw.synth.query(120, shard=9)
+    sc = dict(matrix=oracle.matrix(oracle.MATRIX_BLOSUM62), gap_open=11, gap_extend=1)
+    want, want2 = (oracle.scan(x, r, o, mat=sc["matrix"], gap_open=11, gap_extend=1) for x in (q, q2))
+
+    def visit(db):
+        assert np.array_equal(db.scan(q, **sc), want)
+        return {k: db.stats()[k] for k in ("device_bytes", "n_blocks", "n_long")}
+
+    def more_calls(db):  # the deferred tails' rows, the top-K workspace and id map
+        assert np.array_equal(db.scan_batch([q, q2], **sc), np.stack([want, want2]))
+        ids, best = sw.capi.decode_keys(db.scan_topk(q, 5, **sc))
+        want_ids, want_best = sw.capi.topk(want, 5)
+        assert np.array_equal(ids, want_ids) and np.array_equal(best, want_best)
+        return db.stats()["device_bytes"]
+
+    db = sw.Database(handle, r, o)
+    first = {0: visit(db)}
+    for _ in range(3):
+        for thr in (100, 0):
+            db.set_long_threshold(thr)
+            seen = visit(db)
+            assert first.setdefault(thr, seen) == seen, thr
+    assert first[100] != first[0]  # two layouts
+    db.set_long_threshold(100)
+    assert visit(db) == first[100]
+    after = more_calls(db)
+    assert after >= first[100]["device_bytes"]
+    fresh = sw.Database(handle, r, o, long_threshold=100)
+    assert visit(fresh) == first[100]
+    assert more_calls(fresh) == after
+    fresh.close()
+    db.close()
+
+
 def test_edge_cases(sw, oracle, handle):
     """Empty and ragged subjects, an empty query, custom ids."""
     seqs = ["", "A", "W", "WW", "", "ACDEFGHIKLMNPQRSTVWY" * 7, "X*UO/", "M" * 17]

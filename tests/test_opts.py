@@ -55,7 +55,7 @@ def test_no_environment_read_on_the_scan_path():
     """The library reads SW_* variables only in sw_opts_from_env (VERDICT r04
     item 8): the scan path's choices come from the handle's sw_opts."""
     for src in ("sw_capi.cpp", "sw_kernels.hip", "sw_inter_x2.hip", "sw_intra_x2.hip", "sw_topk.hip",
-                "sw_profile.hip", "sw_synth.hip", "sw_align.hip"):
+                "sw_profile.hip", "sw_synth.hip", "sw_align.hip", "sw_group.cpp", "sw_host.h", "sw_owned.h"):
         text = open(os.path.join(CSRC, src)).read()
         calls = [m.start() for m in re.finditer(r"\bgetenv\(", text)]
         if src != "sw_capi.cpp":
@@ -65,3 +65,21 @@ def test_no_environment_read_on_the_scan_path():
         body = body[:body.index("\n}\n")]
         start = text.index(body)
         assert calls and all(start <= c < start + len(body) for c in calls), "getenv outside sw_opts_from_env"
+
+
+def test_hip_resources_are_created_and_released_in_sw_host_h():
+    """Every HIP resource of the host driver is held by an owner (DESIGN.md,
+    "Who owns a HIP resource"): the calls that create or release device
+    memory, pinned memory, events and streams occur in csrc/sw_host.h, behind
+    the owners' helpers, and in no .cpp file, so no member or local can be
+    released by hand, twice, or not at all."""
+    # (by name, so a function passed as a release argument counts as well as a call)
+    calls = re.compile(r"\b(hipFree|hipHostFree|hipEventDestroy|hipStreamDestroy|hipMalloc|hipHostMalloc)\b"
+                       r"|\b(hipEventCreate|hipStreamCreate)")
+    for src in sorted(os.listdir(CSRC)):
+        if src.endswith(".cpp"):
+            found = [m.group(0) for m in calls.finditer(open(os.path.join(CSRC, src)).read())]
+            assert not found, (src, found)
+    found = {m.group(1) or m.group(2) for m in calls.finditer(open(os.path.join(CSRC, "sw_host.h")).read())}
+    assert found == {"hipFree", "hipHostFree", "hipEventDestroy", "hipStreamDestroy", "hipMalloc", "hipHostMalloc",
+                     "hipEventCreate", "hipStreamCreate"}, found
