@@ -1426,22 +1426,16 @@ int inter_args(Scan& c) {
         a.rescue_count = c.listA;
         a.rescue_list = c.listA + 1;
         if (p.f16) a.rescue_max = c.maxA;  // counters reset before the fork
-        // fp16 exact range: every integer in [-2048, 2048].  The cell
-        // stores true + bias + zero with zero = -2048 + 2 ge, which
-        // nearly doubles the range of true values: the lowest value a
-        // later addition reads is a rebased H of bias -ge (>= -2048:
-        // exact); values further below lose to the floor, which sits at
-        // zero or above, and only need their order.  H grows by <= max S
-        // per cell and the biased cell stores values up to 26 ge above
-        // the true ones (bias (15 + 7 + 2) ge, + 2 ge in the profile).
-        const int zero = -kF16Span + 2 * ge;
-        a.sat_limit = kF16Span - zero - 2 * std::max(c.sc.max_s, 1) - 26 * ge;
-        for (int j = 0; j < 32; ++j) a.f16_step[j] = f16_pair(j * ge + zero);
-        a.f16_gog = f16_pair(go - ge);
-        a.f16_zero = f16_pair(zero);
-        a.f16_diff[0] = f16_pair(4 * ge);
-        a.f16_diff[1] = f16_pair(8 * ge);
-        a.f16_diff[2] = f16_pair(16 * ge);
+        // The biased cell stores true + bias + Z as unsigned integers that
+        // are positive normal fp16 patterns (swplan::cell_range states the
+        // bounds; matrix and table entries are int8, validated to -100..100,
+        // so -128 bounds them).
+        const swplan::CellRange cr = swplan::cell_range(-128, c.sc.max_s, go, ge);
+        a.sat_limit = cr.sat_limit;
+        std::copy(std::begin(cr.step), std::end(cr.step), a.f16_step);
+        a.f16_gog = cr.gog;
+        a.f16_zero = cr.step[0];
+        std::copy(std::begin(cr.diff), std::end(cr.diff), a.f16_diff);
     }
     a.re_last = p.re_last;  // the short last pass (x2s_pass)
     // its blocks: [blk_base, blk_first) by wave groups (the merged launch:

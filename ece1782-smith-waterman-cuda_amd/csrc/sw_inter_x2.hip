@@ -11,21 +11,28 @@
 // costs ~26 SIMD-cycles per 64 cells (profiles/r01_valu_rate_*.txt); one
 // v_pk_* instruction (also ~4.25 cycles) updates TWO cells.
 //
-// The default cell is fp16 with a bias (x2s_pass): cell (r, jj)
-// of an 8-column sub-group stores H + (r % 16 + jj) ge, so both gap
-// extensions are the drift of the bias and an affine cell pair is 5 packed
-// ops (v_pk_fma_f16 for H_diag + S, v_pk_maximum3_f16 for H, v_pk_add_f16
-// for H - (go - ge), a max for E, a max3 for F with the floor), a linear one
-// 3; the running maxima are kept per anti-diagonal.  The lane's low halves run
-// rows [s0, s0 + 32) at column t, the high halves rows [s0 + 32, s0 + 64) at
-// column t - 8, fed through an 8-entry register delay line, so a 64-row pass
-// hands one dword (H | F << 16) per column to the next pass through HBM.
+// The default cell is the biased "fp16" cell (x2s_pass): cell
+// (r, jj) of an 8-column sub-group stores H + (r % 16 + jj) ge, so both gap
+// extensions are the drift of the bias and an affine cell pair is 5 ops
+// (v_add3_u32 for H_diag + S, v_pk_maximum3_f16 for H, v_sub_u32 for H - (go
+// - ge), a packed max for E, a max3 for F with the floor), a linear one 3;
+// the running maxima are kept per anti-diagonal.  Each 16-bit half holds an
+// unsigned integer that is also a positive normal fp16 bit pattern: every
+// addition is a 32-bit integer op on the dword (both halves at once, no carry
+// or borrow across bit 16), and fp16 is only the comparator of the maxima.
+// The lane's low halves run rows [s0, s0 + 32) at column t, the high halves
+// rows [s0 + 32, s0 + 64) at column t - 8, fed through an 8-entry register
+// delay line, so a 64-row pass hands one dword (H | F << 16) per column to the
+// next pass through HBM.
 // The pair (S_low, S_high) is formed without a combine: the LDS images hold
-// (S, 1) and (1, S) and the fma multiplies them.
+// S_low sign-extended to 32 bits and S_high << 16, and one three-operand add
+// sums them onto the diagonal (int16: (S, 1) and (1, S), multiplied).
 //
-// Exactness: every fp16 value carries the offset -2048 + 2 ge, so true scores
-// up to ~4,000 are exact integers; a lane whose maximum reaches the guard band
-// (a.sat_limit) flags its block, which the int16 form of the same kernel
+// Exactness: every stored value is true + bias + Z (swplan::cell_range: Z =
+// 0x2000), an exact integer between 0x0400 and 0x7BFF, where the unsigned
+// order is the fp16 order and a maximum returns one of its inputs bit for
+// bit; a lane whose maximum reaches the guard band (a.sat_limit, true scores
+// of ~4,000) flags its block, which the int16 form of the same kernel
 // re-scores (x2s_block with F16 = false: up to 32767, guard kSat16), and
 // blocks it flags again go to the int32 kernel (sw_int32.h).  Blocks and
 // subjects are listed on the device (sw_kernels.h list_publish / list_take);
@@ -188,17 +195,18 @@ __device__ __forceinline__ void store_bnd(uint32_t* bnd, uint64_t i, const uint3
 // low strip on SG pad columns after it.  Same packed cell as sw_inter_x2; the
 // score pair is lo[code(t)][i] | hi[code(t-SG)][i] with the two images holding
 // the two strips' rows.
-// F16: the images hold the scores as fp16 bit patterns (exact integers).
-__device__ __forceinline__ uint32_t to_f16_bits(uint32_t v16) {
-    return static_cast<uint32_t>(__builtin_bit_cast(uint16_t, static_cast<_Float16>(static_cast<int16_t>(v16))));
-}
+// F16: the images hold the scores as integers for a 32-bit add (stage_x2s).
 
 // Stage the profile images of one pass: img 0 (lo) <- rows [s0, s0+R), img 1
 // (hi) <- rows [s0+R, s0+2R), both when img < 0 (2 x 26 codes x R/8 int4
-// loads of 8 rows each, spread over the lanes).  Each dword pairs a row's
-// score with 1 (1.0 in fp16) in the other half: the kernel forms the pair
-// as lo * hi + H_diag in one v_pk_fma_f16 / v_pk_mad_u16.
-// F16: the images hold S + bias (the column-biased cell's gap extension), and
+// loads of 8 rows each, spread over the lanes).  int16: each dword pairs a
+// row's score with 1 in the other half, and the kernel forms the pair as
+// lo * hi + H_diag in one v_pk_mad_u16.
+// F16: lo holds the low strip's S + bias sign-extended to 32 bits, hi the high
+// strip's (S + bias) << 16, so H_diag + lo + hi (mod 2^32, one v_add3_u32) is
+// H_diag + S in both halves: a negative low score borrows through its sign
+// extension, and nothing else crosses bit 16 while both sums stay in [0,
+// 65535] (swplan::cell_range).  bias: the column-biased cell's gap extension;
 // the first row of each 16-row group S + bias + bias0: the diagonal entering
 // that row still carries the previous row group's bias, 16 ge above its own
 // (bias0 = -16 ge folds the shift back into the profile; see x2s_pass).
@@ -212,7 +220,7 @@ __device__ __forceinline__ void stage_x2s(X2Lds<R>& L, const int16_t* __restrict
                                           int lane, int bias, int bias0, int img, int hi0 = R) {
     constexpr int RD = x2_row_dwords(R);
     constexpr int PER = kImgCodes * (R / 8);  // int4 loads per image
-    constexpr uint32_t one = F16 ? 0x3c00u : 1u;
+    constexpr uint32_t one = 1u;
     const int n = img < 0 ? 2 * PER : PER;
     for (int t = lane; t < n; t += kLanes) {
         const int im = img < 0 ? t / PER : img;
@@ -235,13 +243,15 @@ __device__ __forceinline__ void stage_x2s(X2Lds<R>& L, const int16_t* __restrict
             const int s0v = static_cast<int16_t>(w[e] & 0xffffu), s1v = static_cast<int16_t>(w[e] >> 16);
             // row 8k + 2e of the strip starts a row group when k is even and e = 0
             const int b0 = (F16 && k % 2 == 0 && e == 0) ? bias0 : 0;
-            uint32_t a0 = static_cast<uint32_t>(s0v) & 0xffffu, a1 = static_cast<uint32_t>(s1v) & 0xffffu;
+            const uint32_t a0 = static_cast<uint32_t>(s0v) & 0xffffu, a1 = static_cast<uint32_t>(s1v) & 0xffffu;
             if constexpr (F16) {
-                a0 = to_f16_bits(static_cast<uint32_t>(s0v + bias + b0));
-                a1 = to_f16_bits(static_cast<uint32_t>(s1v + bias));
+                const uint32_t w0 = static_cast<uint32_t>(s0v + bias + b0), w1 = static_cast<uint32_t>(s1v + bias);
+                o[2 * e] = im ? w0 << 16 : w0;
+                o[2 * e + 1] = im ? w1 << 16 : w1;
+            } else {
+                o[2 * e] = im ? (a0 << 16) | one : a0 | (one << 16);
+                o[2 * e + 1] = im ? (a1 << 16) | one : a1 | (one << 16);
             }
-            o[2 * e] = im ? (a0 << 16) | one : a0 | (one << 16);
-            o[2 * e + 1] = im ? (a1 << 16) | one : a1 | (one << 16);
         }
         int4* d = reinterpret_cast<int4*>((im ? L.hi : L.lo) + c * RD + 8 * k);
         d[0] = make_int4(o[0], o[1], o[2], o[3]);
@@ -278,11 +288,11 @@ __device__ __forceinline__ void read_x2a(int4 (&pl)[N], int4 (&ph)[N], uint32_t&
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 
 // The packed cell in two number formats.  int16: wrapping add, saturating
-// subtract, v_pk_max_i16.  fp16 (affine only): v_pk_add_f16 and the gfx950
-// three-input v_pk_maximum3_f16, which folds the 0 floor into E and F
-// (E = max3(E - ge, n, 0)) and H's two maxima into one: 7.5 packed ops per
-// cell pair instead of 9.66 (profiles/r01_f16_rate.txt).  fp16 holds every
-// integer up to 2048 exactly.
+// subtract, v_pk_max_i16.  "fp16": 32-bit integer adds on the dword and the
+// gfx950 three-input v_pk_maximum3_f16 as the comparator, which folds the
+// floor into F and H's two maxima into one (profiles/r01_f16_rate.txt,
+// profiles/r08_int_adds/f16_rate.txt).  The halves are unsigned integers in
+// [0x0400, 0x7BFF]: positive normal fp16 patterns, ordered as the integers.
 template <bool F16>
 struct PkCell;
 
@@ -302,6 +312,15 @@ struct PkCell<true> {
 
 __device__ __forceinline__ h2 max3h(h2 a, h2 b, h2 c) {
     return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c);
+}
+// Both halves' integer sum / difference in one 32-bit op: exact per half as
+// long as neither half's result leaves [0, 65535] (no carry or borrow crosses
+// bit 16; swplan::cell_range states the bounds).
+__device__ __forceinline__ h2 iadd(h2 a, h2 b) {
+    return __builtin_bit_cast(h2, __builtin_bit_cast(uint32_t, a) + __builtin_bit_cast(uint32_t, b));
+}
+__device__ __forceinline__ h2 isub(h2 a, h2 b) {
+    return __builtin_bit_cast(h2, __builtin_bit_cast(uint32_t, a) - __builtin_bit_cast(uint32_t, b));
 }
 
 // SHORT: the block's last pass may take the short form (x2s_pass RL = R - 4);
@@ -359,15 +378,14 @@ struct Best<true> {
         asm volatile("" : "+v"(acc[16]), "+v"(acc[17]), "+v"(acc[18]), "+v"(acc[19]), "+v"(acc[20]),
                      "+v"(acc[21]), "+v"(acc[22]));
     }
-    // the maximum with the bias removed but the offset kept (the true score
-    // may exceed 2048, which fp16 no longer holds exactly; x2s_finish
-    // removes the offset in integers)
+    // the maximum with the bias removed but the offset Z kept (x2s_finish
+    // removes it): acc[k] >= Z, and k ge is far less than Z - 0x0400
     __device__ __forceinline__ h2 value(const InterArgs& a) const {
-        const h2 z = __builtin_bit_cast(h2, a.f16_step[0]);
         h2 b = acc[0];
 #pragma unroll
         for (int k = 1; k < kAcc; ++k)
-            b = __builtin_elementwise_maximum(b, acc[k] - (__builtin_bit_cast(h2, a.f16_step[k]) - z));
+            b = __builtin_elementwise_maximum(
+                b, __builtin_bit_cast(h2, __builtin_bit_cast(uint32_t, acc[k]) - (a.f16_step[k] - a.f16_step[0])));
         return b;
     }
 };
@@ -401,17 +419,26 @@ __device__ __forceinline__ void trace_block(const InterArgs& a, int blk, uint64_
 // Guarded mode: H grows by at most max S per cell, so a lane whose values
 // could have left the exact range has its running maximum in the guard
 // band first — int16: [kSat16, 32767] (or wrapped: negative); fp16:
-// >= a.sat_limit = 2048 - 2 max S, computed exactly — and its block is
-// re-scored from the list by the next stage (int16 packed, then int32).
+// >= a.sat_limit, computed exactly — and its block is re-scored from the
+// list by the next stage (int16 packed, then int32).
+// fp16, a lane past the guard keeps computing.  Its values may reach the NaN
+// patterns (>= 0x7C01), the negative ones (>= 0x8000) or wrap a low half into
+// the high half: that half is the same subject's other strip, so no other
+// lane is touched.  Its accumulators passed the guard while every value was
+// still exact (guard + 2 max S + the largest bias <= 0x7BFF), and from then on
+// they only grow, or turn NaN and stay NaN (a maximum returns its largest
+// input, or a NaN once one comes in; a negative pattern never wins).  The
+// pattern is compared UNSIGNED here, so such a lane always flags.
 // Returns (wave-uniform) whether the block was appended to the rescue list.
 template <bool F16>
 __device__ __forceinline__ bool x2s_finish(const InterArgs& a, int blk, int lane, typename PkCell<F16>::V best) {
     int b;
-    if constexpr (F16)  // offset removed in integers: true scores go up to ~4096
-        b = static_cast<int>(static_cast<float>(__builtin_elementwise_maximum(best.x, best.y))) -
-            static_cast<int>(static_cast<float>(__builtin_bit_cast(h2, a.f16_step[0]).x));
-    else
+    if constexpr (F16) {  // the unsigned patterns' maximum, less the offset Z
+        const uint32_t u = PkCell<F16>::bits(best);
+        b = static_cast<int>(max(u & 0xffffu, u >> 16)) - static_cast<int>(a.f16_step[0] & 0xffffu);
+    } else {
         b = max(static_cast<int>(best.x), static_cast<int>(best.y));
+    }
     const int id = a.lane_ids[static_cast<size_t>(blk) * kLanes + lane];
     if (id >= 0) a.scores[id] = b;
     if (a.rescue_list) {
@@ -516,7 +543,7 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
     const u2 go2 = {static_cast<unsigned short>(a.gap_open), static_cast<unsigned short>(a.gap_open)};
     const u2 ge2 = {static_cast<unsigned short>(a.gap_extend), static_cast<unsigned short>(a.gap_extend)};
     uint32_t* bnd = reinterpret_cast<uint32_t*>(a.bnd_h);
-    // fp16 biased cell constants (exact integers, host-built, SGPRs)
+    // fp16 biased cell constants (integer pairs, host-built, SGPRs)
     static_assert(!F16 || (R % kRowGroup == 0 && SG <= 8), "fp16 row groups");
     h2 gog_h = {}, reb_h = {}, grp_h = {};
     if constexpr (F16) {
@@ -549,15 +576,12 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
     // of the unrolled steps (straight-line code, as the full pass's: a form
     // with one body and wave-uniform skips of 4-row quarters took any height
     // but ran C2 4.6 % slower).
-    //  * The rows left out keep in H the start value of a strip, the floor
-    //    with the bias of column SG - 1, and every rebase takes SG ge off.
-    //    The fp16 maxima read H[RL] as the partner "cell (RL, jj - 1)" of row
-    //    RL - 1 (cell_d): from the first rebase on it lies below the floor of
-    //    the anti-diagonal it is compared on, which every real cell reaches,
-    //    so the maxima are unchanged; it only ever decreases, by finite
-    //    steps, so it is never NaN or +inf (far below the exact range it may
-    //    stop moving or, with a large ge over a long pass, reach -inf: it is
-    //    only compared, and max3 with -inf is the other two's maximum).
+    //  * The rows left out are never computed or rebased.  The fp16 maxima
+    //    read H[RL] as the partner "cell (RL, jj - 1)" of row RL - 1
+    //    (cell_d): it is parked at the pattern +0.0, below every floor (Z and
+    //    above), which every real cell reaches, so the maxima are unchanged.
+    //    It is only compared, never added to: rebased as an integer it would
+    //    wrap over a long pass and borrow from the other half.
     //  * The low strip's bottom row is row RL - 1, of bias (11 + jj) ge (RL =
     //    28 or 44), while col_start and the hi image's first row take the
     //    delay line at the last row group's bias, (15 + jj) ge for H and (16 +
@@ -588,7 +612,7 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
     V H[R];
     V E[AFFINE ? R : 1];
 #pragma unroll
-    for (int r = 0; r < R; ++r) H[r] = P::from(F16 ? a.f16_step[r % kRowGroup + SG - 1] : 0u);
+    for (int r = 0; r < R; ++r) H[r] = P::from(F16 && r < RL ? a.f16_step[r % kRowGroup + SG - 1] : 0u);
 #pragma unroll
     for (int r = 0; r < (AFFINE ? R : 1); ++r) E[r] = P::from(F16 ? a.f16_zero : 0u);
     uint32_t dtop = dtop0;             // packed H of row -1 at the previous step
@@ -697,16 +721,17 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
             // what crosses the sub-group boundary (H as the next diagonal, E)
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                // (short form: of the rows left out only H[RL], the maxima's partner, is read)
-                if (r <= RL) H[r] = H[r] - reb_h;
+                // (short form: the rows left out stay parked, H[RL] included)
+                if (r < RL) H[r] = isub(H[r], reb_h);
                 if constexpr (AFFINE)
-                    if (r < RL) E[r] = E[r] - reb_h;
+                    if (r < RL) E[r] = isub(E[r], reb_h);
             }
-            dtop = P::bits(P::from(dtop) - reb_h);
+            dtop -= P::bits(reb_h);
         }
         // One cell pair: row r of column jj.  `up`, `diag` and `f` roll down
-        // the column; slo = (S_low strip, 1), shi = (1, S_high strip), so
-        // slo * shi + diag is the pair's H_diag + S in one packed op.
+        // the column; int16: slo = (S_low strip, 1), shi = (1, S_high strip),
+        // so slo * shi + diag is the pair's H_diag + S in one packed op;
+        // fp16: slo + shi + diag as 32-bit integers (stage_x2s).
         auto cell = [&](const int r, const int jj, V& up, V& diag, V& f, const V slo, const V shi) {
             if constexpr (F16 && !AFFINE) {
                 // Biased linear cell: H~ = H + (r % 16 + jj) g, so the left and
@@ -714,8 +739,8 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
                 // H~ = max(max3(left, up, H_diag + S + 2 g), floor): 3 packed
                 // ops per cell pair + the anti-diagonal maxima.
                 const int rg = r % kRowGroup;
-                if (rg == 0 && r > 0) up = up - grp_h;  // next row group: its bias restarts at 0
-                const h2 t = max3h(H[r], up, __builtin_elementwise_fma(slo, shi, diag));
+                if (rg == 0 && r > 0) up = isub(up, grp_h);  // next row group: its bias restarts at 0
+                const h2 t = max3h(H[r], up, iadd(iadd(slo, shi), diag));
                 const h2 h = __builtin_elementwise_maximum(t, __builtin_bit_cast(h2, a.f16_step[rg + jj]));
                 h2& acc = best.acc[rg + jj];
                 if (jj & 1) {
@@ -749,15 +774,16 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
         // 16 + jj) ge, so both gap extensions are the drift of the bias: E' =
         // max(E', m) along the row and F~ = max3(F~, m, floor) down the column
         // with m = H~ - go + ge, no subtraction.  F carries the 0 floor (H >=
-        // 0), b of the next row.  5 packed ops per cell pair (+ about half a
+        // 0), b of the next row.  5 ops per cell pair, the two sums 32-bit
+        // integer ops and the three maxima packed fp16 (+ about half a
         // max3 for the maximum, 2 per row per sub-group for the column rebase,
         // 4 per column for the row-group resets).
         auto cell_d = [&](const int r, const int jj, V& up, V& diag, V& f, const V d) {
           if constexpr (F16 && AFFINE) {
             const int rg = r % kRowGroup;
-            if (rg == 0 && r > 0) f = f - grp_h;  // next row group: its bias restarts at 0
+            if (rg == 0 && r > 0) f = isub(f, grp_h);  // next row group: its bias restarts at 0
             const h2 h = max3h(E[r], f, d);
-            const h2 m = h - gog_h;
+            const h2 m = isub(h, gog_h);
             E[r] = __builtin_elementwise_maximum(E[r], m);
             f = max3h(f, m, __builtin_bit_cast(h2, a.f16_step[rg + jj + 1]));
             h2& acc = best.acc[rg + jj];
@@ -776,8 +802,8 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
         auto col_done = [&](const V up, const V f, const int jj) {
             if constexpr (kSh && F16) {
                 // `up` and `f` are row RL - 1's: up to the last row group's bias
-                dl_h[jj] = P::bits(up + dsh_h);
-                if constexpr (AFFINE) dl_f[jj] = P::bits(f + dsh_h);
+                dl_h[jj] = P::bits(iadd(up, dsh_h));
+                if constexpr (AFFINE) dl_f[jj] = P::bits(iadd(f, dsh_h));
             } else {
                 dl_h[jj] = P::bits(up);
                 if constexpr (AFFINE) dl_f[jj] = P::bits(f);
@@ -792,11 +818,11 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
             // fp16: row 0's diagonal keeps the last row group's bias (the
             // profile's row 0 takes it back); the linear cell's up term drops it
             up = P::from(u);
-            if constexpr (F16 && !AFFINE) up = up - grp_h;
+            if constexpr (F16 && !AFFINE) up = isub(up, grp_h);
             diag = P::from(dtop);
             dtop = u;
             if constexpr (AFFINE) f = P::from(hi_lo(bin[jj], dl_f[jj]));
-            if constexpr (F16) f = f - grp_h;
+            if constexpr (F16) f = isub(f, grp_h);
         };
         V up = P::from(0u), diag = P::from(0u), f = P::from(0u);
 #pragma unroll
@@ -829,8 +855,7 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
 #pragma unroll
                 for (int i = 0; i < CR; ++i)
                     if (i < n)
-                        dd[i] = __builtin_elementwise_fma(P::from(word(pl, i)), P::from(word(ph, i)),
-                                                          i == 0 ? diag : H[CR * k + i - 1]);
+                        dd[i] = P::from(word(pl, i) + word(ph, i) + P::bits(i == 0 ? diag : H[CR * k + i - 1]));
 #pragma unroll
                 for (int i = 0; i < CR; ++i)
                     if (i < n) asm volatile("" : "+v"(dd[i]));

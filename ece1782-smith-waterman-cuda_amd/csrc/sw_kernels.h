@@ -98,15 +98,15 @@ struct InterArgs {
     int32_t blk_first;
     // fp16 kernel: a lane whose running maximum reaches this flags its block
     int32_t sat_limit;
-    // fp16 kernel, biased cell (sw_inter_x2.hip): f16_step[j] = the packed
-    // fp16 pair (j * gap_extend + f16 offset), j = 0..31, and f16_gog =
-    // packed (gap_open - gap_extend); host-built so they stay in SGPRs
-    // All fp16 cell values carry the offset f16_zero = (z, z), z = -2048 +
-    // 2 ge: fp16 holds every integer in [-2048, 2048] exactly, so the
-    // shifted cell is exact for true values up to ~4096 (max/add commute
-    // with the shift; sw_capi.cpp states the bound).  f16_step[j] is then
-    // the pair (j ge + z), and f16_diff the unshifted pairs (4 ge, 8 ge,
-    // 16 ge): the rebase per sub-group of 4 or 8 columns, the row-group reset.
+    // fp16 kernel, biased cell (sw_inter_x2.hip): 16-bit unsigned integer
+    // pairs, host-built (swplan::cell_range) so they stay in SGPRs.  Every
+    // cell value carries the offset Z, f16_zero = (Z, Z): the values are
+    // added as integers and compared as the positive normal fp16 patterns
+    // they are.  f16_step[j] = the pair (j * gap_extend + Z), j = 0..31,
+    // f16_gog = (gap_open - gap_extend) (2^16 + 1), which may be negative
+    // (open below extend) and is subtracted as one dword, and f16_diff the pairs
+    // (4 ge, 8 ge, 16 ge): the rebase per sub-group of 4 or 8 columns, the
+    // row-group reset.
     uint32_t f16_step[32];
     uint32_t f16_gog;
     uint32_t f16_zero;

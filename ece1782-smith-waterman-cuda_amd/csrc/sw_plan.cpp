@@ -443,6 +443,42 @@ PlanScoring plan_scoring_pssm(const int8_t* rows, int32_t qlen, int go, int ge) 
     return plan_scoring_max(mx, go, ge);
 }
 
+// The biased cell's constants and the range of its patterns.  The guard is
+// the fp16 cell's of earlier rounds, true scores of 4096 - 28 ge - 2 max S
+// (which blocks are re-scored does not depend on the cell's format); the
+// format would hold ~29,000.
+//  * Highest: a lane below the guard has every H below it, H grows by at most
+//    max S per cell, the diagonal sum adds one more entry, and a stored value
+//    sits up to 26 ge above the true one (bias (15 + 7 + 2) ge, + 2 ge in the
+//    profile): top = Z + sat_limit + 2 max S + 26 ge.
+//  * Lowest: a floor is Z or above; below it go the rebased H, E and row -1
+//    (8 ge), m = H - (go - ge), the row-group resets (16 ge), a row group's
+//    first profile row (16 ge less) and the diagonal sum's entry, at most
+//    once each: lowest = Z - go - 27 ge - 2 max |S|, the bound of the
+//    admission rule 2 max S + 27 ge + go < 1024 with the matrix's negative
+//    entries counted too.
+// Z = 0x2000 leaves both ends thousands away from kCellMin and kCellMax for
+// every admitted scheme over int8 entries.
+CellRange cell_range(int min_s, int max_s, int go, int ge) {
+    CellRange c;
+    c.z = 0x2000;
+    const int ms = std::max(max_s, 1), abs_s = std::max({ms, -min_s, 0});
+    // v in both halves as ONE 32-bit integer, v (2^16 + 1): adding or
+    // subtracting it moves both halves by v, also for a negative v (go < ge),
+    // whose dword is not two equal 16-bit patterns
+    auto pair = [](int v) { return static_cast<uint32_t>(v) * 0x00010001u; };
+    for (int j = 0; j < 32; ++j) c.step[j] = pair(j * ge + c.z);
+    c.gog = pair(go - ge);
+    c.diff[0] = pair(4 * ge);
+    c.diff[1] = pair(8 * ge);
+    c.diff[2] = pair(16 * ge);
+    c.sat_limit = 4096 - 28 * ge - 2 * ms;
+    c.lowest = c.z - go - 27 * ge - 2 * abs_s;
+    c.guard = c.z + c.sat_limit;
+    c.top = c.guard + 2 * ms + 26 * ge;
+    return c;
+}
+
 ScanPlan scan_plan(const PlanDb& db, int32_t qlen, const PlanScoring& s, bool intra_i16_first, int32_t i16_span) {
     const sw_opts& O = *db.opts;
     const int max_s = s.max_s, go = s.go, ge = s.ge;

@@ -128,6 +128,27 @@ struct ScanPlan {
     void set_drain(bool got_rows);
 };
 
+// The inter scan's biased "fp16" cell (sw_inter_x2.hip x2s_pass): each 16-bit
+// half of a cell dword holds the unsigned integer true + bias + Z.  Sums and
+// differences are 32-bit integer ops on the dword and the maxima are packed
+// fp16 ops, so every value an addition or a maximum reads must be a positive
+// normal fp16 pattern, [kCellMin, kCellMax]: there the unsigned order is the
+// fp16 order, a maximum returns one of its inputs bit for bit whatever the
+// kernel's denormal mode, and no carry or borrow crosses bit 16.
+constexpr int kCellMin = 0x0400, kCellMax = 0x7BFF;
+struct CellRange {
+    int z = 0;               // the offset Z of every stored value
+    uint32_t step[32] = {};  // InterArgs::f16_step: the pair (j ge + Z) in both halves, the floor of bias j ge
+    uint32_t gog = 0;        // f16_gog: (go - ge) (2^16 + 1), the dword whose subtraction takes go - ge off both halves
+    uint32_t diff[3] = {};   // f16_diff: the pairs (4 ge, 8 ge, 16 ge)
+    int sat_limit = 0;       // a lane whose true maximum reaches this flags its block
+    int lowest = 0;          // the lowest pattern an addition or a maximum can read
+    int guard = 0;           // the guard's pattern at bias 0: Z + sat_limit
+    int top = 0;             // the highest pattern of a lane below the guard: guard + 2 max S + the largest bias
+};
+// min_s, max_s: bounds of the scoring matrix's (or table's) entries.
+CellRange cell_range(int min_s, int max_s, int go, int ge);
+
 // intra_i16_first, i16_span: the adaptive routes (sw_capi.cpp
 // adapt_intra_i16_first, adapt_inter_i16_span; span within 0 .. nblocks).
 ScanPlan scan_plan(const PlanDb& db, int32_t qlen, const PlanScoring& s, bool intra_i16_first, int32_t i16_span);

@@ -17,6 +17,7 @@
             w[c] = 0x40004000u + c;                                                   \
         }                                                                             \
         uint32_t y = 0x3c003c00u ^ (seed & 1), z = 0x00000000u;                       \
+        const uint32_t sg = 0x00100010u | seed; /* uniform: an SGPR operand */        \
         for (int it = 0; it < ITERS; ++it) {                                          \
             _Pragma("unroll") for (int c = 0; c < CHAINS; ++c) INSTR_##INSTR(v[c], w[c]); \
         }                                                                             \
@@ -41,6 +42,35 @@
     "v_pk_add_f16 %0, %1, %2\n v_pk_add_f16 %1, %1, %2\n v_pk_maximum3_f16 %1, %1, %0, %3\n" \
     "v_pk_add_f16 %0, %0, %2\n v_pk_maximum3_f16 %0, %0, %1, %3\n"                      \
     "v_pk_maximum3_f16 %1, %1, %0, %2" : "+v"(x), "+v"(u) : "v"(y), "v"(z))
+// 32-bit integer adds on the packed dword (both halves at once, no carry across bit 16)
+#define INSTR_add3_u32(x, u) asm volatile("v_add3_u32 %0, %0, %1, %2" : "+v"(x) : "v"(y), "v"(z))
+#define INSTR_subrev_u32_s(x, u) asm volatile("v_subrev_u32_e32 %0, %1, %0" : "+v"(x) : "s"(sg))
+// the 5-op affine cell pair of the biased inter scan: diagonal sum, H, H - (go - ge), E, F
+#define INSTR_pair_f16(x, u) asm volatile(                                              \
+    "v_pk_fma_f16 %0, %2, %3, %0\n v_pk_maximum3_f16 %1, %1, %0, %2\n"                 \
+    "v_pk_add_f16 %0, %1, %2\n v_pk_max_f16 %1, %1, %0\n"                              \
+    "v_pk_maximum3_f16 %0, %0, %1, %3" : "+v"(x), "+v"(u) : "v"(y), "v"(z))
+// the same pair with the two additions as 32-bit integer ops; fp16 only compares
+#define INSTR_pair_int(x, u) asm volatile(                                              \
+    "v_add3_u32 %0, %0, %2, %3\n v_pk_maximum3_f16 %1, %1, %0, %2\n"                   \
+    "v_subrev_u32_e32 %0, %4, %1\n v_pk_max_f16 %1, %1, %0\n"                          \
+    "v_pk_maximum3_f16 %0, %0, %1, %3" : "+v"(x), "+v"(u) : "v"(y), "v"(z), "s"(sg))
+// where the subtrahend sits: a VGPR, an SGPR, or folded into an add of its negation
+#define INSTR_sub_u32_v(x, u) asm volatile("v_sub_u32_e32 %0, %0, %1" : "+v"(x) : "v"(y))
+#define INSTR_add_u32_v(x, u) asm volatile("v_add_u32_e32 %0, %0, %1" : "+v"(x) : "v"(y))
+#define INSTR_add_u32_s(x, u) asm volatile("v_add_u32_e32 %0, %1, %0" : "+v"(x) : "s"(sg))
+#define INSTR_sub_u32_clamp(x, u) asm volatile("v_sub_u32_e64 %0, %0, %1 clamp" : "+v"(x) : "v"(y))
+// the integer pair with the subtrahend in a VGPR, and with two 2-operand adds for the diagonal
+#define INSTR_pair_int_v(x, u) asm volatile(                                            \
+    "v_add3_u32 %0, %0, %2, %3\n v_pk_maximum3_f16 %1, %1, %0, %2\n"                   \
+    "v_sub_u32_e32 %0, %1, %2\n v_pk_max_f16 %1, %1, %0\n"                             \
+    "v_pk_maximum3_f16 %0, %0, %1, %3" : "+v"(x), "+v"(u) : "v"(y), "v"(z))
+#define INSTR_pair_int_2add(x, u) asm volatile(                                         \
+    "v_add_u32_e32 %0, %0, %2\n v_add_u32_e32 %0, %0, %3\n v_pk_maximum3_f16 %1, %1, %0, %2\n" \
+    "v_sub_u32_e32 %0, %1, %2\n v_pk_max_f16 %1, %1, %0\n"                             \
+    "v_pk_maximum3_f16 %0, %0, %1, %3" : "+v"(x), "+v"(u) : "v"(y), "v"(z))
+BODY(add3_u32) BODY(subrev_u32_s) BODY(pair_f16) BODY(pair_int)
+BODY(sub_u32_v) BODY(add_u32_v) BODY(add_u32_s) BODY(sub_u32_clamp) BODY(pair_int_v) BODY(pair_int_2add)
 BODY(pk_maximum3_f16) BODY(pk_add_f16) BODY(pk_max_f16) BODY(pk_max_i16) BODY(cell_i16) BODY(cell_f16)
 
 __global__ void probe(uint32_t* o) {
@@ -61,6 +91,11 @@ int main() {
         {"v_pk_maximum3_f16", k_pk_maximum3_f16, 1}, {"v_pk_add_f16", k_pk_add_f16, 1},
         {"v_pk_max_f16", k_pk_max_f16, 1}, {"v_pk_max_i16", k_pk_max_i16, 1},
         {"cell pair int16 (9 ops)", k_cell_i16, 9}, {"cell pair fp16 (8 ops)", k_cell_f16, 8},
+        {"v_add3_u32", k_add3_u32, 1}, {"v_subrev_u32 (SGPR)", k_subrev_u32_s, 1},
+        {"biased pair fp16 (5 ops)", k_pair_f16, 5}, {"biased pair int add (5 ops)", k_pair_int, 5},
+        {"v_sub_u32 (VGPR)", k_sub_u32_v, 1}, {"v_add_u32 (VGPR)", k_add_u32_v, 1},
+        {"v_add_u32 (SGPR)", k_add_u32_s, 1}, {"v_sub_u32 clamp (VGPR)", k_sub_u32_clamp, 1},
+        {"int pair, VGPR sub (5 ops)", k_pair_int_v, 5}, {"int pair, 2 adds (6 ops)", k_pair_int_2add, 6},
     };
     hipDeviceProp_t p;
     hipGetDeviceProperties(&p, 0);
