@@ -4,11 +4,13 @@
 //   * pad/encode the query and upload it to __constant__ (:267-299)
 //       -> a 32 x qpad int8 query PROFILE (score of every residue code against
 //          every query row, pre-biased by the gap for the linear kernels),
-//          built on the host and copied once per query (tiny: 32 B/row);
+//          built on the device by the scan's first launch (sw_profile.hip)
+//          from the query's codes (tiny: 32 B/row);
 //   * re-pack the whole database into managed memory on every query,
 //     longest-first, 32 lanes per block (:301-371)
 //       -> sw_db_create packs ONCE into 64-lane blocks of 16-residue groups,
-//          sorted longest-first, and keeps the result resident in HBM;
+//          sorted longest-first (sw_pack.cpp), and keeps the result resident
+//          in HBM;
 //   * launch in chunks with cudaDeviceSynchronize after each (:332-354,379)
 //       -> one asynchronous launch per kernel on the handle's stream;
 //   * read managed scores back in packing order (:383-390)
@@ -23,16 +25,20 @@
 #include <new>
 #include <numeric>
 #include <string>
-#include <thread>
 #include <unordered_map>
 #include <vector>
 
+#include "sw_dbfile.h"
 #include "sw_host.h"
+#include "sw_pack.h"
+#include "sw_parallel.h"
 #include "sw_plan.h"
+#include "sw_synth_host.h"
 
 using swk::DevPtr;
 using swk::Event;
 using swk::HostPtr;
+using swk::parallel_for;
 using swk::Stream;
 
 namespace {
@@ -134,35 +140,6 @@ void init_lut() {
 
 int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
-int default_threads() {
-    unsigned n = std::thread::hardware_concurrency();
-    if (n == 0) n = 4;
-    return static_cast<int>(std::min(16u, n));  // GPU boxes expose many more CPUs than our share
-}
-
-// f(i) for i in [0, n) on up to default_threads() threads, `grain` indices
-// per grab (at least one grab per thread).
-template <class F>
-void parallel_for(int64_t n, F&& f, int64_t grain = 64) {
-    const int nt = static_cast<int>(std::min<int64_t>(default_threads(), std::max<int64_t>(1, n / grain)));
-    if (nt <= 1) {
-        for (int64_t i = 0; i < n; ++i) f(i);
-        return;
-    }
-    std::atomic<int64_t> next{0};
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t)
-        th.emplace_back([&] {
-            for (;;) {
-                const int64_t i0 = next.fetch_add(grain);
-                if (i0 >= n) break;
-                const int64_t i1 = std::min(n, i0 + grain);
-                for (int64_t i = i0; i < i1; ++i) f(i);
-            }
-        });
-    for (auto& t : th) t.join();
-}
-
 // A vector element type that resize() leaves uninitialised (the database's
 // host copy is filled by parallel copies right after).
 template <class T>
@@ -180,27 +157,6 @@ struct NoInitAlloc : std::allocator<T> {
         else ::new (static_cast<void*>(p)) U(std::forward<A>(a)...);
     }
 };
-
-// Subject indices sorted by length, longest first, stable (file order
-// within a length): a counting sort when lengths are bounded, else
-// std::stable_sort.
-std::vector<int64_t> length_order(const std::vector<int64_t>& offs, int64_t n) {
-    std::vector<int64_t> order(n);
-    int64_t maxl = 0;
-    for (int64_t k = 0; k < n; ++k) maxl = std::max(maxl, offs[k + 1] - offs[k]);
-    if (maxl > (int64_t(1) << 22)) {
-        std::iota(order.begin(), order.end(), 0);
-        std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) {
-            return offs[x + 1] - offs[x] > offs[y + 1] - offs[y];
-        });
-        return order;
-    }
-    std::vector<int64_t> start(static_cast<size_t>(maxl) + 2, 0);
-    for (int64_t k = 0; k < n; ++k) ++start[static_cast<size_t>(maxl - (offs[k + 1] - offs[k]) + 1)];
-    for (size_t l = 1; l < start.size(); ++l) start[l] += start[l - 1];
-    for (int64_t k = 0; k < n; ++k) order[start[static_cast<size_t>(maxl - (offs[k + 1] - offs[k]))]++] = k;
-    return order;
-}
 
 }  // namespace
 
@@ -456,16 +412,9 @@ struct sw_db {
         size_t device_bytes = 0;
     };
     Layout lay;
-    // what build_db derives with it (overwritten by the next build)
-    int64_t nblocks = 0;
-    int64_t packed_cells = 0;
-    size_t res_bytes = 0;
-    int64_t nlong = 0;
-    int32_t long_max = 0;
-    size_t lres_bytes = 0;
-    std::vector<uint32_t> h_blk_groups;  // block widths (16-column groups), widest first
-    std::vector<int64_t> h_blk_res;      // unpadded residues per block
-    std::vector<int32_t> h_llen;         // long subjects' lengths, longest first
+    // the layout's shape (sw_pack.h), assigned by the build that uploaded it:
+    // the counts, and of the tables blk_groups, blk_res and llen
+    swpack::Shape shape;
     int rid_identity = -1;               // result ids are 0 .. n-1 in order (1), or not (0); -1 unknown
     uint64_t list_epoch = 0;             // g_fault_epoch when the lists were last known clean
     // the intra chain's order (adapt_intra_i16_first): the fp16 pass's
@@ -518,12 +467,12 @@ swplan::PlanDb plan_view(const sw_db* db) {
     swplan::PlanDb v;
     v.n = db->n;
     v.residues = db->residues;
-    v.nblocks = db->nblocks;
-    v.nlong = db->nlong;
+    v.nblocks = db->shape.nblocks;
+    v.nlong = db->shape.nlong;
     v.long_threshold = db->long_threshold;
-    v.long_max = db->long_max;
-    v.blk_groups = db->h_blk_groups.data();
-    v.llen = db->h_llen.data();
+    v.long_max = db->shape.long_max;
+    v.blk_groups = db->shape.blk_groups.data();
+    v.llen = db->shape.llen.data();
     v.opts = &db->h->opts;
     v.cus = db->h->cus;
     return v;
@@ -540,7 +489,7 @@ swplan::PlanDb plan_view(const sw_db* db) {
 // here once its readback has completed (long_pass records it).  opt =
 // sw_opts intra_i16_first: 0 / 1 never / always, else the observations.
 bool adapt_intra_i16_first(sw_db* db, uint64_t skey, int32_t qlen, int32_t opt) {
-    if (readback_take(db->lcount) && 3 * static_cast<int64_t>(db->lcount.host.get()[0]) > db->nlong) {
+    if (readback_take(db->lcount) && 3 * static_cast<int64_t>(db->lcount.host.get()[0]) > db->shape.nlong) {
         const Readback::Obs& o = db->lcount.last;
         bool seen = false;
         for (auto& e : db->i16_first)
@@ -592,7 +541,7 @@ int32_t adapt_inter_i16_span(sw_db* db, uint64_t skey, int32_t qlen, int32_t opt
         for (const auto& o : db->i16_span)
             if (o.key == skey && o.qlen <= qlen) i16_span = std::max(i16_span, o.span);
     }
-    return static_cast<int32_t>(std::min<int64_t>(std::max(i16_span, 0), db->nblocks));
+    return static_cast<int32_t>(std::min<int64_t>(std::max(i16_span, 0), db->shape.nblocks));
 }
 
 // sw_db_reset_adaptive: forget what earlier scans observed.
@@ -619,88 +568,11 @@ int upload(DevPtr<T>& d, const std::vector<T>& v, hipStream_t s, size_t* acc) {
     return SW_OK;
 }
 
-// ---- synthetic databases -------------------------
-// Swiss-Prot composition (percent), codes 0..19 = A R N D C Q E G H I L K M F
-// P S T W Y V (the same table as synth.py).
-const double kSwissProtFreq[20] = {8.25, 5.53, 4.06, 5.45, 1.37, 3.93, 6.75, 7.07, 2.27, 5.96,
-                                   9.66, 5.84, 2.42, 3.86, 4.70, 6.56, 5.34, 1.08, 2.92, 6.87};
-constexpr uint64_t kLenSalt = 0x4C454E475448ull;  // "LENGTH"
-
-// Acklam's rational approximation of the standard normal quantile.
-double norm_quantile(double p) {
-    static const double a[6] = {-3.969683028665376e+01, 2.209460984245205e+02, -2.759285104469687e+02,
-                                1.383577518672690e+02, -3.066479806614716e+01, 2.506628277459239e+00};
-    static const double b[5] = {-5.447609879822406e+01, 1.615858368580409e+02, -1.556989798598866e+02,
-                                6.680131188771972e+01, -1.328068155288572e+01};
-    static const double c[6] = {-7.784894002430293e-03, -3.223964580411365e-01, -2.400758277161838e+00,
-                                -2.549732539343734e+00, 4.374664141464968e+00, 2.938163982698783e+00};
-    static const double d[4] = {7.784695709041462e-03, 3.224671290700398e-01, 2.445134137142996e+00,
-                                3.754408661907416e+00};
-    const double pl = 0.02425;
-    if (p < pl) {
-        const double q = std::sqrt(-2 * std::log(p));
-        return (((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) /
-               ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1);
-    }
-    if (p > 1 - pl) {
-        const double q = std::sqrt(-2 * std::log(1 - p));
-        return -(((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) /
-               ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1);
-    }
-    const double q = p - 0.5, r = q * q;
-    return (((((a[0] * r + a[1]) * r + a[2]) * r + a[3]) * r + a[4]) * r + a[5]) * q /
-           (((((b[0] * r + b[1]) * r + b[2]) * r + b[3]) * r + b[4]) * r + 1);
-}
-
-struct SynthTables {
-    int32_t len[4096];     // log-normal length quantiles: median 290, sigma 0.657, in [5, 35213]
-    uint8_t lut[65536];    // uniform u16 -> residue code
-    uint8_t lut_stored[65536];  // ... as stored on the device (swk::kStored)
-    SynthTables() {
-        for (int k = 0; k < 4096; ++k) {
-            const double z = norm_quantile((k + 0.5) / 4096.0);
-            const double L = std::nearbyint(std::exp(std::log(290.0) + 0.657 * z));
-            len[k] = static_cast<int32_t>(std::min(35213.0, std::max(5.0, L)));
-        }
-        double sum = 0, acc = 0;
-        for (double f : kSwissProtFreq) sum += f;
-        int64_t edges[20];
-        for (int c = 0; c < 20; ++c) {
-            acc += kSwissProtFreq[c] / sum;
-            edges[c] = static_cast<int64_t>(std::nearbyint(acc * 65536.0));
-        }
-        edges[19] = 65536;
-        int c = 0;
-        for (int v = 0; v < 65536; ++v) {
-            while (c < 19 && edges[c] <= v) ++c;
-            lut[v] = static_cast<uint8_t>(c);
-            lut_stored[v] = swk::kStored[c];
-        }
-    }
-};
-
-const SynthTables& synth_tables() {
-    static const SynthTables t;
-    return t;
-}
-
-int32_t synth_length(uint64_t seed, uint64_t gid) {
-    return synth_tables().len[swk::synth_hash(seed, gid, kLenSalt) >> 52];
-}
-
-void synth_residues(uint64_t seed, uint64_t gid, int64_t L, uint8_t* out) {
-    const uint8_t* lut = synth_tables().lut;
-    for (int64_t j = 0; j < L; j += 4) {
-        const uint64_t h = swk::synth_hash(seed, gid, static_cast<uint64_t>(j >> 2));
-        for (int e = 0; e < 4 && j + e < L; ++e) out[j + e] = lut[(h >> (16 * e)) & 0xffffu];
-    }
-}
-
 // Residues of subject k (host): stored, or regenerated for synthetic dbs.
 void subject_residues(const sw_db* db, int64_t k, uint8_t* out) {
     const int64_t L = db->h_offsets[k + 1] - db->h_offsets[k];
     if (db->synthetic)
-        synth_residues(db->seed, static_cast<uint64_t>(db->id_base + db->h_ids[k]), L, out);
+        swk::synth_residues(db->seed, static_cast<uint64_t>(db->id_base + db->h_ids[k]), L, out);
     else
         std::memcpy(out, db->h_residues.data() + db->h_offsets[k], L);
 }
@@ -748,82 +620,24 @@ int staged_upload(sw_handle* h, uint8_t* dev, const std::vector<uint64_t>& bound
     return SW_OK;
 }
 
-// Pack: sort by length (descending, stable), route subjects longer than the
-// threshold to the intra kernel, deal the rest into 64-lane blocks of
-// 16-residue groups.  Lanes past a subject's end hold kPadCode.
+// The subjects as the packer reads them (sw_pack.h).
+swpack::Subjects subjects_view(const sw_db* db) {
+    swpack::Subjects v;
+    v.n = db->n;
+    v.offsets = db->h_offsets.data();
+    v.ids = db->h_ids.data();
+    v.residues = db->synthetic ? nullptr : db->h_residues.data();
+    return v;
+}
+
+// The device half of packing: the layout's shape is sw_pack.cpp's; allocate
+// it, upload the residues as the packer fills them (or generate them in
+// place), upload its tables, and keep the shape.
 int build_db(sw_db* db) {
     hipStream_t s = db->h->stream.get();
-    const int64_t n = db->n;
-    const std::vector<int64_t> order = length_order(db->h_offsets, n);
-    auto len = [&](int64_t k) { return db->h_offsets[k + 1] - db->h_offsets[k]; };
-    int64_t nlong = 0;
-    while (nlong < n && len(order[nlong]) > db->long_threshold) ++nlong;
-
-    // ---- intra (long) part: plain concatenation, 64-byte aligned starts
-    std::vector<uint64_t> loff(nlong + 1);
-    std::vector<int32_t> llen(nlong), lid(nlong);
-    uint64_t ltotal = 0;
-    for (int64_t k = 0; k < nlong; ++k) {
-        const int64_t src = order[k];
-        loff[k] = ltotal;
-        llen[k] = static_cast<int32_t>(len(src));
-        lid[k] = db->h_ids[src];
-        ltotal += round_up(len(src), 64);
-    }
-    loff[nlong] = ltotal;
-
-    // ---- inter part
-    const int64_t nshort = n - nlong;
-    const int64_t nblocks = (nshort + swk::kLanes - 1) / swk::kLanes;
-    std::vector<uint64_t> blk_off(nblocks + 1);
-    std::vector<uint32_t> blk_groups(nblocks), blk_cols(nblocks);
-    std::vector<int32_t> lane_ids(nblocks * swk::kLanes, -1);
-    std::vector<int64_t> blk_res(nblocks, 0);  // unpadded residues per block
-    uint64_t total = 0;
-    for (int64_t b = 0; b < nblocks; ++b) {
-        const int64_t first = nlong + b * swk::kLanes;  // longest subject of the block
-        const int64_t w = round_up(len(order[first]), swk::kGroupCols);
-        blk_off[b] = total;
-        blk_groups[b] = static_cast<uint32_t>(w / swk::kGroupCols);
-        blk_cols[b] = static_cast<uint32_t>(round_up(len(order[first]), 8));
-        total += static_cast<uint64_t>(blk_groups[b]) * swk::kGroupBytes;
-    }
-    blk_off[nblocks] = total;
-    std::vector<int32_t> lane_len(db->synthetic ? nblocks * swk::kLanes : 0, 0);
-    parallel_for(nblocks, [&](int64_t b) {
-        for (int l = 0; l < swk::kLanes; ++l) {
-            const int64_t k = nlong + b * swk::kLanes + l;
-            if (k >= n) break;
-            const int64_t src = order[k];
-            lane_ids[b * swk::kLanes + l] = db->h_ids[src];
-            blk_res[b] += len(src);
-            if (db->synthetic) lane_len[b * swk::kLanes + l] = static_cast<int32_t>(len(src));
-        }
-    });
-    // one block's bytes: [group][lane][16 codes], kPadCode past each subject;
-    // codes are stored as swk::kStored (the profile rows follow it)
-    auto stored = [](uint8_t* d, const uint8_t* p, int64_t m) {
-        for (int64_t j = 0; j < m; ++j) d[j] = swk::kStored[p[j]];
-    };
-    auto fill_block = [&](int64_t b, uint8_t* dst) {
-        std::memset(dst, swk::kPadCode, static_cast<size_t>(blk_groups[b]) * swk::kGroupBytes);
-        for (int l = 0; l < swk::kLanes; ++l) {
-            const int64_t k = nlong + b * swk::kLanes + l;
-            if (k >= n) break;
-            const int64_t src = order[k], L = len(src);
-            const uint8_t* p = db->h_residues.data() + db->h_offsets[src];
-            uint8_t* d = dst + l * swk::kGroupCols;
-            int64_t j = 0;
-            for (; j + swk::kGroupCols <= L; j += swk::kGroupCols, d += swk::kGroupBytes) stored(d, p + j, swk::kGroupCols);
-            if (j < L) stored(d, p + j, L - j);
-        }
-    };
-    auto fill_long = [&](int64_t k, uint8_t* dst) {
-        const int64_t src = order[k];
-        std::memset(dst, swk::kPadCode, loff[k + 1] - loff[k]);
-        stored(dst, db->h_residues.data() + db->h_offsets[src], len(src));
-    };
-    blk_off.pop_back();
+    const swpack::Subjects subj = subjects_view(db);
+    swpack::Shape sh = swpack::plan(subj, db->long_threshold, db->synthetic);
+    const uint64_t total = sh.total, ltotal = sh.ltotal;
 
     size_t acc = 0;
     int rc;
@@ -835,32 +649,35 @@ int build_db(sw_db* db) {
         acc += total + ltotal;
     } else {
         // residues through pinned staging, packed in parallel chunks
-        std::vector<uint64_t> bounds(blk_off);
-        bounds.push_back(total);
         if (total) {
             HIPCHECK(swk::dev_alloc(db->lay.d_res, total));
-            if ((rc = staged_upload(db->h, db->lay.d_res.get(), bounds, fill_block))) return rc;
+            if ((rc = staged_upload(db->h, db->lay.d_res.get(), sh.blk_off,
+                                    [&](int64_t b, uint8_t* dst) { swpack::fill_block(subj, sh, b, dst); })))
+                return rc;
         }
         if (ltotal) {
             HIPCHECK(swk::dev_alloc(db->lay.d_lres, ltotal));
-            if ((rc = staged_upload(db->h, db->lay.d_lres.get(), loff, fill_long))) return rc;
+            if ((rc = staged_upload(db->h, db->lay.d_lres.get(), sh.loff,
+                                    [&](int64_t k, uint8_t* dst) { swpack::fill_long(subj, sh, k, dst); })))
+                return rc;
         }
         acc += total + ltotal;
     }
-    if ((rc = upload(db->lay.d_blk_off, blk_off, s, &acc))) return rc;
-    if ((rc = upload(db->lay.d_blk_groups, blk_groups, s, &acc))) return rc;
-    if ((rc = upload(db->lay.d_blk_cols, blk_cols, s, &acc))) return rc;
-    if ((rc = upload(db->lay.d_lane_ids, lane_ids, s, &acc))) return rc;
-    loff.pop_back();
-    if ((rc = upload(db->lay.d_loff, loff, s, &acc))) return rc;
-    if ((rc = upload(db->lay.d_llen, llen, s, &acc))) return rc;
-    if ((rc = upload(db->lay.d_lid, lid, s, &acc))) return rc;
+    sh.blk_off.pop_back();  // the kernels' tables have no end entry
+    sh.loff.pop_back();
+    if ((rc = upload(db->lay.d_blk_off, sh.blk_off, s, &acc))) return rc;
+    if ((rc = upload(db->lay.d_blk_groups, sh.blk_groups, s, &acc))) return rc;
+    if ((rc = upload(db->lay.d_blk_cols, sh.blk_cols, s, &acc))) return rc;
+    if ((rc = upload(db->lay.d_lane_ids, sh.lane_ids, s, &acc))) return rc;
+    if ((rc = upload(db->lay.d_loff, sh.loff, s, &acc))) return rc;
+    if ((rc = upload(db->lay.d_llen, sh.llen, s, &acc))) return rc;
+    if ((rc = upload(db->lay.d_lid, sh.lid, s, &acc))) return rc;
     if (db->synthetic) {
         DevPtr<int32_t> d_lane_len;  // the fill's inputs, released after it has run
         DevPtr<uint8_t> d_lut;
         size_t tmp = 0;
-        if ((rc = upload(d_lane_len, lane_len, s, &tmp))) return rc;
-        const SynthTables& T = synth_tables();
+        if ((rc = upload(d_lane_len, sh.lane_len, s, &tmp))) return rc;
+        const swk::SynthTables& T = swk::synth_tables();
         HIPCHECK(swk::dev_alloc(d_lut, sizeof T.lut_stored));
         HIPCHECK(hipMemcpyAsync(d_lut.get(), T.lut_stored, sizeof T.lut_stored, hipMemcpyHostToDevice, s));
         swk::SynthFill f{};
@@ -869,28 +686,21 @@ int build_db(sw_db* db) {
         f.blk_groups = db->lay.d_blk_groups.get();
         f.lane_local = db->lay.d_lane_ids.get();
         f.lane_len = d_lane_len.get();
-        f.nblocks = nblocks;
+        f.nblocks = sh.nblocks;
         f.lres = db->lay.d_lres.get();
         f.loff = db->lay.d_loff.get();
         f.llen = db->lay.d_llen.get();
         f.lid = db->lay.d_lid.get();
-        f.nlong = static_cast<int32_t>(nlong);
+        f.nlong = static_cast<int32_t>(sh.nlong);
         f.seed = db->seed;
         f.id_base = db->id_base;
         f.lut = d_lut.get();
         HIPCHECK(swk::launch_synth_fill(f, s));
         HIPCHECK(hipStreamSynchronize(s));
     }
-    HIPCHECK(hipStreamSynchronize(s));  // host vectors go out of scope
-    db->h_blk_groups = blk_groups;
-    db->h_blk_res = blk_res;
-    db->h_llen = llen;
-    db->res_bytes = total;
-    db->lres_bytes = ltotal;
-    db->nblocks = nblocks;
-    db->nlong = nlong;
-    db->long_max = nlong ? static_cast<int32_t>(len(order[0])) : 0;
-    db->packed_cells = static_cast<int64_t>(total);  // one byte per scanned (lane, column)
+    HIPCHECK(hipStreamSynchronize(s));  // the uploads' sources go away
+    sh.release_upload_tables();
+    db->shape = std::move(sh);
     db->lay.device_bytes = acc;
     db->lay.built = true;
     return SW_OK;
@@ -899,7 +709,7 @@ int build_db(sw_db* db) {
 // Boundary rows are only needed when the query spans more than one strip;
 // allocate on first need and keep.
 int ensure_bnd(sw_db* db, bool affine, bool intra_f) {
-    const size_t res = db->res_bytes * 4, lres = db->lres_bytes * 4;
+    const size_t res = db->shape.total * 4, lres = db->shape.ltotal * 4;
     const struct {
         DevPtr<int32_t>& p;
         size_t bytes;
@@ -920,8 +730,8 @@ int ensure_bnd(sw_db* db, bool affine, bool intra_f) {
 // tails in stream order); a refused size is not tried again for this layout.
 bool ensure_rbnd(sw_db* db, bool affine, bool intra_f) {
     DevPtr<int32_t>* const p[4] = {&db->lay.d_rbnd_h, &db->lay.d_rbnd_f, &db->lay.d_rlbnd_h, &db->lay.d_rlbnd_f};
-    const size_t sz[4] = {db->res_bytes * 4, affine ? db->res_bytes * 4 : 0, db->lres_bytes * 4,
-                          (affine || intra_f) ? db->lres_bytes * 4 : 0};
+    const size_t sz[4] = {db->shape.total * 4, affine ? db->shape.total * 4 : 0, db->shape.ltotal * 4,
+                          (affine || intra_f) ? db->shape.ltotal * 4 : 0};
     size_t need = 0;
     for (int k = 0; k < 4; ++k)
         if (sz[k] && !p[k]->get()) need += sz[k];
@@ -1326,9 +1136,9 @@ int scan_lists(Scan& c, bool defer) {
     // lists A and B, the largest flagged block, a spare word, the dequeue
     // heads of A and B (the merged launch's drain); every entry starts at -1
     // (sw_kernels.h: whoever takes an entry resets it)
-    const int64_t rstride = 2 * (db->nblocks + 1) + 4;
-    const int64_t lstride = 2 * (db->nlong + 1) + 2;  // intra lists 1 and 2, their heads
-    if (p.rescue && db->nblocks && !db->lay.d_rescue.get()) {
+    const int64_t rstride = 2 * (db->shape.nblocks + 1) + 4;
+    const int64_t lstride = 2 * (db->shape.nlong + 1) + 2;  // intra lists 1 and 2, their heads
+    if (p.rescue && db->shape.nblocks && !db->lay.d_rescue.get()) {
         HIPCHECK(swk::dev_alloc(db->lay.d_rescue, 2 * rstride * sizeof(int32_t)));
         HIPCHECK(hipMemsetAsync(db->lay.d_rescue.get(), 0xff, 2 * rstride * sizeof(int32_t), h->stream.get()));
         db->lay.device_bytes += 2 * rstride * sizeof(int32_t);
@@ -1360,15 +1170,15 @@ int scan_lists(Scan& c, bool defer) {
     if (p.drain && (rc = join_tails(h))) return rc;
     if (db->lay.d_rescue.get()) {
         c.listA = db->lay.d_rescue.get() + c.par * rstride;
-        c.listB = c.listA + db->nblocks + 1;
-        c.maxA = c.listA + 2 * (db->nblocks + 1);
+        c.listB = c.listA + db->shape.nblocks + 1;
+        c.maxA = c.listA + 2 * (db->shape.nblocks + 1);
         c.headA = c.maxA + 2;
         if (p.lpt && h->opts.lpt_persist != 0) c.lpt_next = c.maxA + 1;  // the spare word
     }
     if (db->lay.d_lrescue.get()) {
         c.list1 = db->lay.d_lrescue.get() + c.par * lstride;
-        c.list2 = c.list1 + db->nlong + 1;
-        c.head1 = c.list2 + db->nlong + 1;
+        c.list2 = c.list1 + db->shape.nlong + 1;
+        c.head1 = c.list2 + db->shape.nlong + 1;
     }
     c.deferred = !p.drain && defer && (!(p.multi_inter || p.multi_intra) || ensure_rbnd(db, p.affine, p.intra_x2));
     return SW_OK;
@@ -1380,7 +1190,7 @@ int scan_lists(Scan& c, bool defer) {
 int scan_profiles(Scan& c, const QuerySrc& src, const int8_t* mat) {
     const swplan::ScanPlan& p = c.plan;
     const bool d = p.drain;
-    int32_t* const cA = (p.rescue && c.db->nblocks) ? c.listA : nullptr;
+    int32_t* const cA = (p.rescue && c.db->shape.nblocks) ? c.listA : nullptr;
     int32_t* const c1 = p.intra_x2 ? c.list1 : nullptr;
     int32_t* const reset[10] = {cA, (cA && p.f16) ? c.listB : nullptr, (cA && p.f16) ? c.maxA : nullptr, c1,
                                 c1 ? c.list2 : nullptr, d ? c.headA : nullptr, d ? c.headA + 1 : nullptr,
@@ -1403,7 +1213,7 @@ int inter_args(Scan& c) {
     a.blk_groups = db->lay.d_blk_groups.get();
     a.blk_cols = db->lay.d_blk_cols.get();
     a.lane_ids = db->lay.d_lane_ids.get();
-    a.nblocks = static_cast<int32_t>(db->nblocks);
+    a.nblocks = static_cast<int32_t>(db->shape.nblocks);
     a.prof = c.P.dev + (p.shape.x2s ? c.P.off16 : c.P.off8);
     a.prof_stride = c.P.stride;
     a.qpad = p.qpad_inter;
@@ -1416,7 +1226,7 @@ int inter_args(Scan& c) {
         if (!db->lay.h_trace.get()) {
             // one entry per block, then one per workgroup of a merged
             // launch (at most nblocks inter + nlong / 8 intra workgroups)
-            db->lay.trace_entries = static_cast<size_t>(2 * db->nblocks + db->nlong + 8);
+            db->lay.trace_entries = static_cast<size_t>(2 * db->shape.nblocks + db->shape.nlong + 8);
             HIPCHECK(swk::host_alloc(db->lay.h_trace, 32 * db->lay.trace_entries, hipHostMallocMapped));
             std::memset(db->lay.h_trace.get(), 0, 32 * db->lay.trace_entries);
         }
@@ -1445,7 +1255,7 @@ int inter_args(Scan& c) {
         a.blk_first = p.npair;
         a.blk_quad = p.nquad;
         a.blk_tri = p.ntri ? 1 : 0;
-        a.blk_tail = static_cast<int32_t>(db->nblocks) - p.ntail;
+        a.blk_tail = static_cast<int32_t>(db->shape.nblocks) - p.ntail;
     } else if (p.npair) {
         a.blk_base = p.nr;
         a.blk_first = std::max(p.npair, p.nr);
@@ -1463,7 +1273,7 @@ void intra_args(Scan& c) {
     ia.subj_off = db->lay.d_loff.get();
     ia.subj_len = db->lay.d_llen.get();
     ia.subj_id = db->lay.d_lid.get();
-    ia.nsubj = static_cast<int32_t>(db->nlong);
+    ia.nsubj = static_cast<int32_t>(db->shape.nlong);
     ia.prof = c.P.dev + c.P.intra_off;
     ia.qpad = c.plan.qpad_intra;
     ia.gap_open = c.sc.go;
@@ -1498,11 +1308,11 @@ void intra_x2_args(Scan& c) {
 }
 
 int scan_args(Scan& c) {
-    if (c.db->nlong) {
+    if (c.db->shape.nlong) {
         intra_args(c);
         if (c.plan.intra_x2) intra_x2_args(c);
     }
-    return c.db->nblocks ? inter_args(c) : SW_OK;
+    return c.db->shape.nblocks ? inter_args(c) : SW_OK;
 }
 
 // The four rescue stages, on boundary rows r:
@@ -1790,18 +1600,18 @@ int print_rescue_stats(const Scan& c) {
     int32_t wmin = 1 << 30, wmax = 0, bmin = 1 << 30, bmax = -1;
     for (int32_t b : ids) {
         if (b < 0) continue;  // (taken entries are reset to -1: a drained list shows counts only)
-        res += db->h_blk_res[b];
-        wmin = std::min<int32_t>(wmin, db->h_blk_groups[b] * 16);
-        wmax = std::max<int32_t>(wmax, db->h_blk_groups[b] * 16);
+        res += db->shape.blk_res[b];
+        wmin = std::min<int32_t>(wmin, db->shape.blk_groups[b] * 16);
+        wmax = std::max<int32_t>(wmax, db->shape.blk_groups[b] * 16);
         bmin = std::min(bmin, b);
         bmax = std::max(bmax, b);
     }
     std::fprintf(stderr,
                  "rescue: qlen %d go %d ge %d: inter %d/%lld blocks flagged (ids %d..%d, widths %d..%d, "
                  "%lld of %lld residues), %d again; pairs %d; intra %d/%lld flagged, %d again\n",
-                 c.qlen, c.sc.go, c.sc.ge, cA, static_cast<long long>(db->nblocks), bmin, bmax, wmin, wmax,
+                 c.qlen, c.sc.go, c.sc.ge, cA, static_cast<long long>(db->shape.nblocks), bmin, bmax, wmin, wmax,
                  static_cast<long long>(res), static_cast<long long>(db->residues), cB, c.plan.npair, l1,
-                 static_cast<long long>(db->nlong), l2);
+                 static_cast<long long>(db->shape.nlong), l2);
     return SW_OK;
 }
 
@@ -1878,18 +1688,18 @@ int scan_impl_body(sw_handle* h, const sw_db* cdb, const QuerySrc& src, int32_t*
         // fork: the side streams start when the main stream reaches ev[0]
         // (the merged launch has none: its scan time runs from ev[6])
         MARK(0, h->stream.get());
-        if (db->nlong && (rc = long_pass(c))) return rc;
-        MARK(1, db->nlong ? h->side.get() : h->stream.get());
-        if (db->nblocks && (rc = inter_pass(c))) return rc;
+        if (db->shape.nlong && (rc = long_pass(c))) return rc;
+        MARK(1, db->shape.nlong ? h->side.get() : h->stream.get());
+        if (db->shape.nblocks && (rc = inter_pass(c))) return rc;
     }
     if ((rc = deferred_tails(c))) return rc;
 
     // join (the merged launch has no separate inter end, nor a side stream
     // to join), rank, and the end event
-    if (!db->nblocks)
+    if (!db->shape.nblocks)
         for (int k = 6; k < 8; ++k) MARK(k, h->stream.get());
     if (!p.lpt) MARK(2, h->stream.get());
-    if (db->nlong && !p.lpt) HIPCHECK(hipStreamWaitEvent(h->stream.get(), h->ev[1].get(), 0));
+    if (db->shape.nlong && !p.lpt) HIPCHECK(hipStreamWaitEvent(h->stream.get(), h->ev[1].get(), 0));
     // the scan completes on the handle's stream: so do earlier deferred tails
     if (!c.deferred && (rc = join_tails(h))) return rc;
     if (rq && (rc = rank_after(h, db, scores_dev, *rq))) return rc;
@@ -2204,30 +2014,12 @@ int sw_db_create(sw_handle* h, const uint8_t* residues, const int64_t* offsets, 
     return SW_OK;
 }
 
-// ---- binary database file ---------------------------
-namespace {
-constexpr char kDbMagic[8] = {'S', 'W', 'A', 'M', 'D', 'D', 'B', '1'};
-struct DbFileHeader {
-    char magic[8];
-    int64_t n;         // subjects
-    int64_t residues;  // total residue codes
-    int32_t max_len;
-    int32_t version;   // 1
-    uint64_t fnv;      // FNV-1a 64 over offsets, ids and residues
-};
-
-uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
-    const auto* b = static_cast<const uint8_t*>(p);
-    for (size_t k = 0; k < n; ++k) h = (h ^ b[k]) * 1099511628211ull;
-    return h;
-}
-}  // namespace
-
+// ---- binary database file (sw_dbfile.cpp) ----------------------------------
 int sw_db_save(const sw_db* db, const char* path) {
     if (!db || !path) return fail(SW_E_INVALID, "null argument");
     // length-sorted (descending, stable), ids kept: loading gives identical scores[id]
     const int64_t n = db->n;
-    const std::vector<int64_t> order = length_order(db->h_offsets, n);
+    const std::vector<int64_t> order = swpack::length_order(db->h_offsets.data(), n);
     auto len = [&](int64_t k) { return db->h_offsets[k + 1] - db->h_offsets[k]; };
     std::vector<int64_t> offs(n + 1, 0);
     std::vector<int32_t> ids(n);
@@ -2238,65 +2030,21 @@ int sw_db_save(const sw_db* db, const char* path) {
         offs[k + 1] = offs[k] + len(src);
         ids[k] = db->h_ids[src];
     }
-    DbFileHeader hd{};
-    std::memcpy(hd.magic, kDbMagic, 8);
-    hd.n = n;
-    hd.residues = db->residues;
-    hd.max_len = db->max_len;
-    hd.version = 1;
-    uint64_t f = 1469598103934665603ull;
-    f = fnv1a(f, offs.data(), offs.size() * sizeof(int64_t));
-    f = fnv1a(f, ids.data(), ids.size() * sizeof(int32_t));
-    hd.fnv = fnv1a(f, res.data(), res.size());
-    FILE* fp = std::fopen(path, "wb");
-    if (!fp) return fail(SW_E_IO, std::string("cannot open ") + path);
-    bool ok = std::fwrite(&hd, sizeof hd, 1, fp) == 1 &&
-              std::fwrite(offs.data(), sizeof(int64_t), offs.size(), fp) == offs.size() &&
-              (n == 0 || std::fwrite(ids.data(), sizeof(int32_t), ids.size(), fp) == ids.size()) &&
-              (res.empty() || std::fwrite(res.data(), 1, res.size(), fp) == res.size());
-    ok = (std::fclose(fp) == 0) && ok;
-    if (!ok) return fail(SW_E_IO, std::string("write failed: ") + path);
-    return SW_OK;
+    return swdbfile::write(path, offs, ids, res, db->max_len);
 }
 
 int sw_db_load(sw_handle* h, const char* path, sw_db** out) {
     if (!h || !path || !out) return fail(SW_E_INVALID, "null argument");
     *out = nullptr;
-    FILE* fp = std::fopen(path, "rb");
-    if (!fp) return fail(SW_E_IO, std::string("cannot open ") + path);
-    DbFileHeader hd{};
     std::vector<int64_t> offs;
     std::vector<int32_t> ids;
     std::vector<uint8_t> res;
-    int rc = SW_OK;
-    if (std::fread(&hd, sizeof hd, 1, fp) != 1 || std::memcmp(hd.magic, kDbMagic, 8) != 0 || hd.version != 1 ||
-        hd.n < 0 || hd.residues < 0 || hd.n > (int64_t(1) << 40) || hd.residues > (int64_t(1) << 44)) {
-        rc = fail(SW_E_IO, std::string("not a database file (sw_db_save format 1): ") + path);
-    } else {
-        try {
-            offs.resize(hd.n + 1);
-            ids.resize(hd.n);
-            res.resize(static_cast<size_t>(hd.residues));
-        } catch (...) {
-            rc = fail(SW_E_NOMEM, "out of host memory");
-        }
-        if (!rc && (std::fread(offs.data(), sizeof(int64_t), offs.size(), fp) != offs.size() ||
-                    (hd.n && std::fread(ids.data(), sizeof(int32_t), ids.size(), fp) != ids.size()) ||
-                    (hd.residues && std::fread(res.data(), 1, res.size(), fp) != res.size())))
-            rc = fail(SW_E_IO, std::string("truncated database file: ") + path);
-    }
-    std::fclose(fp);
-    if (rc) return rc;
-    uint64_t f = 1469598103934665603ull;
-    f = fnv1a(f, offs.data(), offs.size() * sizeof(int64_t));
-    f = fnv1a(f, ids.data(), ids.size() * sizeof(int32_t));
-    if (fnv1a(f, res.data(), res.size()) != hd.fnv || offs.back() != hd.residues)
-        return fail(SW_E_IO, std::string("database file checksum mismatch: ") + path);
-    return sw_db_create(h, res.data(), offs.data(), hd.n, ids.data(), out);
+    if (int rc = swdbfile::read(path, offs, ids, res)) return rc;
+    return sw_db_create(h, res.data(), offs.data(), static_cast<int64_t>(ids.size()), ids.data(), out);
 }
 
 int sw_synth_tables(int32_t* len4096, uint8_t* lut65536) {
-    const SynthTables& T = synth_tables();
+    const swk::SynthTables& T = swk::synth_tables();
     if (len4096) std::memcpy(len4096, T.len, sizeof T.len);
     if (lut65536) std::memcpy(lut65536, T.lut, sizeof T.lut);
     return SW_OK;
@@ -2304,7 +2052,7 @@ int sw_synth_tables(int32_t* len4096, uint8_t* lut65536) {
 
 int sw_synth_lengths(uint64_t seed, int64_t id_base, int64_t n, int32_t* lengths) {
     if (n < 0 || (n > 0 && !lengths) || id_base < 0) return fail(SW_E_INVALID, "null argument");
-    parallel_for(n, [&](int64_t k) { lengths[k] = synth_length(seed, static_cast<uint64_t>(id_base + k)); });
+    parallel_for(n, [&](int64_t k) { lengths[k] = swk::synth_length(seed, static_cast<uint64_t>(id_base + k)); });
     return SW_OK;
 }
 
@@ -2372,19 +2120,19 @@ int sw_db_get_stats(const sw_db* db, sw_db_stats* out) {
     if (!db || !out) return fail(SW_E_INVALID, "null argument");
     out->n_subjects = db->n;
     out->residues = db->residues;
-    out->packed_cells = db->packed_cells;
-    out->n_blocks = db->nblocks;
-    out->n_long = db->nlong;
+    out->packed_cells = static_cast<int64_t>(db->shape.total);  // one byte per scanned (lane, column)
+    out->n_blocks = db->shape.nblocks;
+    out->n_long = db->shape.nlong;
     out->device_bytes = static_cast<int64_t>(db->lay.device_bytes);
     out->max_length = db->max_len;
     out->long_threshold = db->long_threshold;
     out->coop_blocks = db->lay.built ? db->last_ncoop : 0;
     out->coop_residues = 0;
-    for (int32_t b = 0; b < out->coop_blocks; ++b) out->coop_residues += db->h_blk_res[b];
+    for (int32_t b = 0; b < out->coop_blocks; ++b) out->coop_residues += db->shape.blk_res[b];
     out->pair_blocks = db->lay.built ? db->last_npair : 0;
     out->pair_merged = db->lay.built && db->last_pair_merged ? 1 : 0;
     out->pair_residues = 0;
-    for (int32_t b = 0; b < out->pair_blocks; ++b) out->pair_residues += db->h_blk_res[b];
+    for (int32_t b = 0; b < out->pair_blocks; ++b) out->pair_residues += db->shape.blk_res[b];
     out->max_id = db->max_id;
     return SW_OK;
 }
@@ -2423,7 +2171,7 @@ int sw_pssm_create(sw_handle* h, const int8_t* rows, int32_t qlen, sw_pssm** out
     p->h = h;
     p->qlen = qlen;
     p->ld = static_cast<int32_t>(round_up(std::max<int32_t>(qlen, 1), 64));
-    p->hash = fnv1a(1469598103934665603ull, rows, static_cast<size_t>(n));
+    p->hash = swdbfile::fnv1a(swdbfile::kFnvBasis, rows, static_cast<size_t>(n));
     p->max_entry = n ? -128 : 0;
     // the resident image: transposed, [code][ld] (swk::PssmProfileArgs)
     p->image.assign(static_cast<size_t>(SW_ALPHABET) * p->ld, 0);

@@ -1,5 +1,6 @@
-// sw_kernels.h — internal interface between the host driver (sw_capi.cpp)
-// and the gfx950 kernels (sw_kernels.hip).  Not part of the public ABI.
+// sw_kernels.h — internal interface between the host code (the driver
+// sw_capi.cpp, the packer sw_pack.cpp, the planner sw_plan.cpp) and the
+// gfx950 kernels (sw_kernels.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,7 +13,8 @@
 namespace swk {
 
 // Record `msg` as this thread's sw_last_error() text and return `code`
-// (sw_capi.cpp; used by the other host translation units, e.g. sw_group.cpp).
+// (sw_capi.cpp; used by the other host translation units: sw_group.cpp,
+// sw_dbfile.cpp).
 int set_error(int code, const std::string& msg);
 
 constexpr int kLanes = 64;        // one database subject per lane (wave64)
@@ -398,7 +400,6 @@ struct SynthFill {
     const uint8_t* lut;          // [65536] uniform u16 -> residue code
 };
 hipError_t launch_synth_fill(const SynthFill& f, hipStream_t s);
-uint64_t synth_hash(uint64_t seed, uint64_t id, uint64_t k);
 
 // Query profiles built on the device (sw_profile.hip) from the query codes
 // and the matrix in the kernel arguments: rows [row0, row1) per launch (at

@@ -17,7 +17,8 @@
 
 namespace swplan {
 
-// What the policies read of a database (sw_capi.cpp sw_db).
+// What the policies read of a database (sw_capi.cpp plan_view: the counts
+// and tables of sw_db's swpack::Shape, sw_pack.h).
 struct PlanDb {
     int64_t n = 0;                        // subjects
     int64_t residues = 0;

@@ -4,27 +4,18 @@
 //
 // Integer-only, so the host and any CPU restatement reproduce it bit for bit
 // (synth.py counter_* functions, tests/test_synth_counter.py):
-//   h(seed, id, k) = mix(seed * G1 + mix(id * G2 + k))         (splitmix64 mix)
+//   h(seed, id, k) = mix(seed * G1 + mix(id * G2 + k))         (sw_synth_hash.h)
 //   length(id)     = LEN_TABLE[h(seed, id, LEN_SALT) >> 52]      (4096 log-normal quantiles)
 //   residue(id, j) = RES_LUT[(h(seed, id, j >> 2) >> (16 * (j & 3))) & 0xffff]
 // RES_LUT maps a uniform u16 to a residue code with Swiss-Prot frequencies.
-// The host computes the lengths and the block layout (O(n)); these kernels
-// write the residue bytes straight into the packed layouts, so a 6.25M-
-// subject shard (2.25 GB) appears in HBM without a host copy or a PCIe
-// transfer.
+// The host computes the lengths (sw_synth_host.cpp) and the block layout
+// (sw_pack.cpp), both O(n); these kernels write the residue bytes straight
+// into the packed layouts, so a 6.25M-subject shard (2.25 GB) appears in HBM
+// without a host copy or a PCIe transfer.
 #include "sw_kernels.h"
+#include "sw_synth_hash.h"
 
 namespace swk {
-
-__host__ __device__ inline uint64_t syn_mix(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__host__ __device__ inline uint64_t syn_hash(uint64_t seed, uint64_t id, uint64_t k) {
-    return syn_mix(seed * 0x9E3779B97F4A7C15ull + syn_mix(id * 0xD6E8FEB86659FD93ull + k));
-}
 
 // inter part: one workgroup (64 lanes) per block, 16 residues per lane per
 // group, one 16-byte store per lane per group
@@ -102,7 +93,5 @@ hipError_t launch_synth_fill(const SynthFill& f, hipStream_t s) {
     }
     return hipSuccess;
 }
-
-uint64_t synth_hash(uint64_t seed, uint64_t id, uint64_t k) { return syn_hash(seed, id, k); }
 
 }  // namespace swk

@@ -55,7 +55,9 @@ def test_no_environment_read_on_the_scan_path():
     """The library reads SW_* variables only in sw_opts_from_env (VERDICT r04
     item 8): the scan path's choices come from the handle's sw_opts."""
     for src in ("sw_capi.cpp", "sw_kernels.hip", "sw_inter_x2.hip", "sw_intra_x2.hip", "sw_topk.hip",
-                "sw_profile.hip", "sw_synth.hip", "sw_align.hip", "sw_group.cpp", "sw_host.h", "sw_owned.h"):
+                "sw_profile.hip", "sw_synth.hip", "sw_align.hip", "sw_group.cpp", "sw_host.h", "sw_owned.h",
+                "sw_pack.cpp", "sw_pack.h", "sw_parallel.h", "sw_dbfile.cpp", "sw_dbfile.h",
+                "sw_synth_host.cpp", "sw_synth_host.h", "sw_synth_hash.h"):
         text = open(os.path.join(CSRC, src)).read()
         calls = [m.start() for m in re.finditer(r"\bgetenv\(", text)]
         if src != "sw_capi.cpp":
