@@ -64,17 +64,46 @@ __host__ __device__ constexpr int x2_row_dwords(int R) { return (R / 4) % 2 == 1
 constexpr int kImgCodes = kPadCode + 1;
 
 // One wave's profile images: `lo` / `hi` for the two strips of a pass.
-// (Copies for column 0 of every sub-group, one sub-group's bias lower, would
-// save the per-sub-group rebase of H: 2 % fewer VALU instructions on C2, but
-// at 77 KB of LDS per pair workgroup the scan ran 2 % SLOWER beside the
-// long-subject kernel, 7.43 against 7.25 ms per step; not kept.)
-template <int R>
+// COL0 (the affine fp16 cell): a third image `hi0` = hi - SG ge in BOTH halves
+// of the dword (mod 2^32), read by the high strip at column 0 of every
+// sub-group, so that H_diag + lo + hi0 is the diagonal sum of the rebased H
+// bit for bit and H (and row -1's H, dtop) are not rebased at all: 33 VALU
+// less per sub-group (x2s_pass).  One image is enough since the sum is a
+// 32-bit integer add: the constant for both halves rides in one dword.
+// Measured (round 10, profiles/r10_col0_image/): the
+// full-height sub-group loop 1,558 -> 1,525 VALU, the short one 1,390 -> 1,362;
+// 3,744 B more LDS per wave, the merged affine launch 60.8 -> 75.8 KB per
+// workgroup, still 2 workgroups per CU; C2, six alternating runs of the
+// parent's tree and this one, 11,594-11,598 -> 11,776-11,798 GCUPS (+1.7 %).
+// (Round 1's form, copies of BOTH fp16 images at 77 KB per pair workgroup,
+// ran 2 % slower beside the long-subject kernel, then a launch of its own.)
+template <int R, bool COL0 = false>
 struct __attribute__((aligned(16))) X2Lds {  // 16-byte aligned: the waves' images are read by ds_read_b128
     static constexpr int kImg = kImgCodes * x2_row_dwords(R);
     uint32_t lo[kImg];
     uint32_t hi[kImg];
 };
-static_assert(sizeof(X2Lds<32>) % 16 == 0 && sizeof(X2Lds<48>) % 16 == 0, "image alignment");
+template <int R>
+struct __attribute__((aligned(16))) X2Lds<R, true> {
+    static constexpr int kImg = kImgCodes * x2_row_dwords(R);
+    uint32_t lo[kImg];
+    uint32_t hi[kImg];
+    uint32_t hi0[kImg];
+};
+// hi0's distance behind hi in 16-byte slots: it rides in the ds_read_b128
+// offset field beside the chunk offset (16 bits), no address register
+template <int R>
+constexpr int x2_col0_slots() { return X2Lds<R, true>::kImg / 4; }
+static_assert(sizeof(X2Lds<32>) % 16 == 0 && sizeof(X2Lds<48>) % 16 == 0 && sizeof(X2Lds<32, true>) % 16 == 0,
+              "image alignment");
+using X2LdsCol0 = X2Lds<32, true>;
+static_assert(__builtin_offsetof(X2LdsCol0, hi0) - __builtin_offsetof(X2LdsCol0, hi) == 16 * x2_col0_slots<32>() &&
+                  __builtin_offsetof(X2LdsCol0, hi0) % 16 == 0 && 16 * x2_col0_slots<32>() + 4 * 32 < 65536,
+              "hi0 sits a whole number of 16-byte slots behind hi, within the ds offset field");
+static_assert(sizeof(X2Lds<48>) == 2 * sizeof(uint32_t) * X2Lds<48>::kImg, "the linear 48-row form holds two images");
+// which instantiations carry the column-0 image
+template <bool AFFINE, bool F16>
+constexpr bool x2_col0() { return AFFINE && F16; }
 
 template <int N>
 __device__ __forceinline__ uint32_t word(const int4 (&v)[N], int w) {
@@ -215,9 +244,11 @@ __device__ __forceinline__ void store_bnd(uint32_t* bnd, uint64_t i, const uint3
 // 8-byte halves.  (The short pass reads the first R - 4 rows of either image;
 // the rows after them are staged all the same, from inside the padded
 // profile: s0 + R - 4 + R < s0 + 2 R <= qpad.)
-template <int R, bool F16>
-__device__ __forceinline__ void stage_x2s(X2Lds<R>& L, const int16_t* __restrict__ prof, int stride, int s0,
-                                          int lane, int bias, int bias0, int img, int hi0 = R) {
+// COL0: wherever hi is written, hi0 = hi - reb (reb: SG ge in both halves, a
+// host-built SGPR) is written from the same words.
+template <int R, bool F16, bool COL0>
+__device__ __forceinline__ void stage_x2s(X2Lds<R, COL0>& L, const int16_t* __restrict__ prof, int stride, int s0,
+                                          int lane, int bias, int bias0, int img, uint32_t reb, int hi0 = R) {
     constexpr int RD = x2_row_dwords(R);
     constexpr int PER = kImgCodes * (R / 8);  // int4 loads per image
     constexpr uint32_t one = 1u;
@@ -256,6 +287,13 @@ __device__ __forceinline__ void stage_x2s(X2Lds<R>& L, const int16_t* __restrict
         int4* d = reinterpret_cast<int4*>((im ? L.hi : L.lo) + c * RD + 8 * k);
         d[0] = make_int4(o[0], o[1], o[2], o[3]);
         d[1] = make_int4(o[4], o[5], o[6], o[7]);
+        if constexpr (COL0) {
+            if (im) {
+                int4* d0 = d + x2_col0_slots<R>();  // (the same address: the distance is a store offset)
+                d0[0] = make_int4(o[0] - reb, o[1] - reb, o[2] - reb, o[3] - reb);
+                d0[1] = make_int4(o[4] - reb, o[5] - reb, o[6] - reb, o[7] - reb);
+            }
+        }
     }
 }
 
@@ -271,13 +309,15 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
 // read_x2 for the two-strips images from precomputed LDS byte addresses of
 // the two code rows (one v_mad each per column): the per-step tie to `dep`
 // keeps the reads from being hoisted, and the chunk offset folds into the
-// ds_read_b128 offset field.
+// ds_read_b128 offset field.  c0: 16-byte slots from the hi image to the one
+// this column reads (hi0 at column 0 of a sub-group, X2Lds), a constant of
+// the unrolled step that joins the chunk offset in that field.
 template <int N>
 __device__ __forceinline__ void read_x2a(int4 (&pl)[N], int4 (&ph)[N], uint32_t& aa, uint32_t& ab, int k,
-                                         uint32_t dep) {
+                                         uint32_t dep, int c0 = 0) {
     asm volatile("" : "+v"(aa), "+v"(ab) : "v"(dep));
     lds_int4* a = reinterpret_cast<lds_int4*>(static_cast<uintptr_t>(aa)) + N * k;
-    lds_int4* b = reinterpret_cast<lds_int4*>(static_cast<uintptr_t>(ab)) + N * k;
+    lds_int4* b = reinterpret_cast<lds_int4*>(static_cast<uintptr_t>(ab)) + N * k + c0;
 #pragma unroll
     for (int q = 0; q < N; ++q) {
         pl[q] = __builtin_bit_cast(int4, a[q]);
@@ -326,17 +366,17 @@ __device__ __forceinline__ h2 isub(h2 a, h2 b) {
 // SHORT: the block's last pass may take the short form (x2s_pass RL = R - 4);
 // the rescue stages, always full height, are built without it
 template <int R, int SG, bool AFFINE, bool F16, int CR = 16, bool SHORT = true>
-__device__ __forceinline__ bool x2s_block(const InterArgs& a, int blk, X2Lds<R>& L, int lane);
+__device__ __forceinline__ bool x2s_block(const InterArgs& a, int blk, X2Lds<R, x2_col0<AFFINE, F16>()>& L, int lane);
 
 // LIST: a rescue stage walking the device-side block list (a separate
 // instantiation, so the list loop costs the scan kernels no registers).
 template <int R, int SG, bool AFFINE, bool F16, bool LIST, int CR = 16>
 __global__ __launch_bounds__(256, 2) void sw_inter_x2s(InterArgs a) {
     static_assert(R % CR == 0 && SG % 4 == 0, "shape");
-    __shared__ __attribute__((aligned(16))) X2Lds<R> lds[kWavesPerWG];
+    __shared__ __attribute__((aligned(16))) X2Lds<R, x2_col0<AFFINE, F16>()> lds[kWavesPerWG];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    X2Lds<R>& L = lds[wave];
+    auto& L = lds[wave];
     if constexpr (LIST) {
         const int n = __builtin_amdgcn_readfirstlane(*a.blk_count);
         for (int i = blockIdx.x * kWavesPerWG + wave; i < n; i += gridDim.x * kWavesPerWG)
@@ -527,7 +567,8 @@ __device__ __forceinline__ void pair_wait(const int* prog, int wave, int need) {
 // The low strip's row -1 input of pass k's first columns was stored by pass
 // k-1's high strip at least one sub-group earlier (ncols >= 32).
 template <int R, int SG, bool AFFINE, bool F16, bool PAIR, int CR = 16, bool CHAIN = false, int RL = R>
-__device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32_t ncols, uint64_t base, int lane,
+__device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R, x2_col0<AFFINE, F16>()>& L, uint32_t ncols,
+                                         uint64_t base, int lane,
                                          int s0, Best<F16>& best, const int4* ring_in, int4* ring_out,
                                          int* tick, const PairSync* ps = nullptr, int chain_passes = 1) {
     static_assert(!(CHAIN && PAIR), "chained passes: single-wave blocks only");
@@ -553,6 +594,10 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
         reb_h = __builtin_bit_cast(h2, a.f16_diff[SG == 4 ? 0 : 1]);
         grp_h = __builtin_bit_cast(h2, a.f16_diff[2]);
     }
+    // the affine fp16 cell: column 0's high-strip reads take the hi0 image
+    constexpr bool COL0 = x2_col0<AFFINE, F16>();
+    constexpr int kC0 = COL0 ? x2_col0_slots<R>() : 0;
+    const uint32_t reb = __builtin_bit_cast(uint32_t, reb_h);
     const bool first = (s0 == 0);
     const bool last = (s0 + 2 * R >= a.qpad);
     // CHAIN: passes in this sweep and its virtual width
@@ -599,7 +644,7 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
     static_assert((R - 4 - 1) % kRowGroup == 11, "the short strip's bottom row: 4 ge under the last row's bias");
     h2 dsh_h = {};
     if constexpr (F16) dsh_h = __builtin_bit_cast(h2, a.f16_diff[0]);  // 4 ge
-    stage_x2s<R, F16>(L, prof16, a.prof_stride, s0, lane, sbias, gbias0, -1, RL);
+    stage_x2s<R, F16>(L, prof16, a.prof_stride, s0, lane, sbias, gbias0, -1, reb, RL);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -609,6 +654,8 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
     // column SG - 1 of a sub-group: H of column -1 (= 0) is (r % 16 + SG - 1)
     // ge, row -1's H (dtop) (SG - 2) ge; rows come in from the boundary with
     // the last row group's bias, (15 + jj) ge for H and (16 + jj) ge for F.
+    // (Affine: H and dtop are never rebased; these column SG - 1 values, here
+    // and at a chain's restarts, are what column 0's sum with hi0 expects.)
     V H[R];
     V E[AFFINE ? R : 1];
 #pragma unroll
@@ -651,7 +698,7 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
     const uint32_t blo = lds_addr(L.lo), bhi = lds_addr(L.hi);
     // LDS addresses of the code rows of the column being prefetched
     uint32_t aa = code_row<RB>(rc, 0, blo), ab = bhi + kPadCode * RB;  // (the pad code's row)
-    read_x2a<CQ>(PL[0], PH[0], aa, ab, 0, 0);
+    read_x2a<CQ>(PL[0], PH[0], aa, ab, 0, 0, kC0);
 
     // sub-groups 0 .. total/SG: the last one runs the high strip only.
     // CHAIN: lo_p / lo_c = the low strip's pass and its first column in that
@@ -674,7 +721,7 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
         const bool next_t1 = CHAIN && wrap && next_lo;
         const bool next_t2 = t1;
         if (t1) {
-            stage_x2s<R, F16>(L, prof16, a.prof_stride, static_cast<int>(lo_p) * 2 * R, lane, sbias, gbias0, 0);
+            stage_x2s<R, F16>(L, prof16, a.prof_stride, static_cast<int>(lo_p) * 2 * R, lane, sbias, gbias0, 0, reb);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 H[r] = P::from(__builtin_amdgcn_perm(P::bits(H[r]), F16 ? a.f16_step[r % kRowGroup + SG - 1] : 0u,
@@ -685,7 +732,7 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
         }
         if (t2) {
             // the high strip enters pass lo_p (the low strip entered it one sub-group ago)
-            stage_x2s<R, F16>(L, prof16, a.prof_stride, static_cast<int>(lo_p) * 2 * R, lane, sbias, gbias0, 1);
+            stage_x2s<R, F16>(L, prof16, a.prof_stride, static_cast<int>(lo_p) * 2 * R, lane, sbias, gbias0, 1, reb);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 H[r] = P::from(__builtin_amdgcn_perm(F16 ? a.f16_step[r % kRowGroup + SG - 1] : 0u, P::bits(H[r]),
@@ -700,7 +747,7 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             aa = code_row<RB>(rc, 0, blo);
             ab = code_row<RB>(rp, 0, bhi);
-            read_x2a<CQ>(PL[0], PH[0], aa, ab, 0, 0);
+            read_x2a<CQ>(PL[0], PH[0], aa, ab, 0, 0, kC0);
         }
         if (next_t1) {
             // pass k's row -1 input: pass k-1's stores of columns 0..SG-1
@@ -718,15 +765,22 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
         }
         if constexpr (F16) {
             // rebase: column SG-1's bias (SG-1) ge -> column 0's 0, applied to
-            // what crosses the sub-group boundary (H as the next diagonal, E)
+            // what crosses the sub-group boundary.  Linear: H (the next
+            // diagonal and the left neighbour) and dtop.  Affine: E alone,
+            // which feeds a maximum; H crosses only as column 0's diagonal
+            // and the maxima of odd columns read the H of this sub-group, so
+            // H and dtop keep column SG - 1's bias and hi0 takes the SG ge
+            // off in the diagonal's v_add3_u32 (X2Lds)
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 // (short form: the rows left out stay parked, H[RL] included)
-                if (r < RL) H[r] = isub(H[r], reb_h);
-                if constexpr (AFFINE)
+                if constexpr (AFFINE) {
                     if (r < RL) E[r] = isub(E[r], reb_h);
+                } else {
+                    if (r < RL) H[r] = isub(H[r], reb_h);
+                }
             }
-            dtop -= P::bits(reb_h);
+            if constexpr (!AFFINE) dtop -= reb;
         }
         // One cell pair: row r of column jj.  `up`, `diag` and `f` roll down
         // the column; int16: slo = (S_low strip, 1), shi = (1, S_high strip),
@@ -776,7 +830,7 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
         // with m = H~ - go + ge, no subtraction.  F carries the 0 floor (H >=
         // 0), b of the next row.  5 ops per cell pair, the two sums 32-bit
         // integer ops and the three maxima packed fp16 (+ about half a
-        // max3 for the maximum, 2 per row per sub-group for the column rebase,
+        // max3 for the maximum, 1 per row per sub-group for E's column rebase,
         // 4 per column for the row-group resets).
         auto cell_d = [&](const int r, const int jj, V& up, V& diag, V& f, const V d) {
           if constexpr (F16 && AFFINE) {
@@ -836,11 +890,11 @@ __device__ __forceinline__ void x2s_pass(const InterArgs& a, X2Lds<R>& L, uint32
                     aa = code_row<RB>(rc, jn, blo);
                     ab = code_row<RB>(rp, jn, bhi);
                 }
-                read_x2a<CQ>(PL[(t + 1) & 1], PH[(t + 1) & 1], aa, ab, kn, dep);
+                read_x2a<CQ>(PL[(t + 1) & 1], PH[(t + 1) & 1], aa, ab, kn, dep, jn == 0 ? kC0 : 0);
             } else if (has_next && !next_t1 && !next_t2) {
                 aa = code_row<RB>(rn, 0, blo);
                 ab = code_row<RB>(rc, 0, bhi);
-                read_x2a<CQ>(PL[(t + 1) & 1], PH[(t + 1) & 1], aa, ab, 0, dep);
+                read_x2a<CQ>(PL[(t + 1) & 1], PH[(t + 1) & 1], aa, ab, 0, dep, kC0);
             }
             if (k == 0) col_start(up, diag, f, jj);
             const int4(&pl)[CQ] = PL[t & 1];
@@ -937,7 +991,7 @@ __device__ __forceinline__ uint32_t block_cols(const InterArgs& a, int blk) {
 }
 
 template <int R, int SG, bool AFFINE, bool F16, int CR, bool SHORT>
-__device__ __forceinline__ bool x2s_block(const InterArgs& a, int blk, X2Lds<R>& L, int lane) {
+__device__ __forceinline__ bool x2s_block(const InterArgs& a, int blk, X2Lds<R, x2_col0<AFFINE, F16>()>& L, int lane) {
     const uint32_t ncols = block_cols(a, blk);
     const uint64_t base = a.blk_off[blk] + static_cast<uint64_t>(lane) * kGroupCols;
     Best<F16> best;
@@ -1021,11 +1075,12 @@ __device__ __forceinline__ int group_ticks(uint32_t ncols, int passes, int SG, i
 
 // The LDS of one workgroup of the group form: the waves' profile images, the
 // rings between consecutive waves of a group (3 for a quad, 2 for two
-// pairs), the partial maxima.  53 KB for pairs, 61 KB for quads: both still
+// pairs), the partial maxima.  46 KB for pairs, 54 KB for quads, with the
+// affine fp16 cell's column-0 images (COL0, X2Lds) 61 and 69 KB: all still
 // leave 2 workgroups per CU, the register-bound occupancy.
-template <int R, int SG, int GMAX>
+template <int R, int SG, int GMAX, bool COL0>
 struct X2pSmem {
-    X2Lds<R> lds[kWavesPerWG];
+    X2Lds<R, COL0> lds[kWavesPerWG];
     int4 ring[kWavesPerWG - kWavesPerWG / GMAX][kRingSlots * (SG / 4) * kLanes];
     uint32_t part[kWavesPerWG][kLanes];
     int prog[kWavesPerWG];  // affine groups: completed sub-groups per wave
@@ -1039,10 +1094,11 @@ struct X2pSmem {
 // (x2s_block): the dispatcher hands out work widest-first across the forms.
 // Returns (per wave) whether this wave appended a block to the rescue list.
 template <int R, int SG, bool AFFINE, bool F16, bool MERGED, int GMAX>
-__device__ __forceinline__ bool x2p_wg(const InterArgs& a, int wgi, int quad_end, X2pSmem<R, SG, GMAX>& sm) {
+__device__ __forceinline__ bool x2p_wg(const InterArgs& a, int wgi, int quad_end,
+                                       X2pSmem<R, SG, GMAX, x2_col0<AFFINE, F16>()>& sm) {
     static_assert(R % 16 == 0 && SG % 4 == 0, "shape");
     static_assert(GMAX == 2 || GMAX == 4, "groups of 2 or 4 waves");
-    X2Lds<R>* lds = sm.lds;
+    auto* lds = sm.lds;
     auto& ring = sm.ring;
     auto& part = sm.part;
     using P = PkCell<F16>;
@@ -1166,7 +1222,7 @@ __device__ __forceinline__ bool x2p_wg(const InterArgs& a, int wgi, int quad_end
 // G = 2: every group block by pairs; G = 4: every group block by quads.
 template <int R, int SG, bool AFFINE, bool F16, bool MERGED, int G>
 __global__ __launch_bounds__(256, kGroupWavesPerEU) void sw_inter_x2p(InterArgs a) {
-    __shared__ __attribute__((aligned(16))) X2pSmem<R, SG, G> sm;
+    __shared__ __attribute__((aligned(16))) X2pSmem<R, SG, G, x2_col0<AFFINE, F16>()> sm;
     x2p_wg<R, SG, AFFINE, F16, MERGED, G>(a, blockIdx.x, MERGED ? a.blk_first : a.nblocks, sm);
 }
 
@@ -1303,7 +1359,8 @@ template <int R, int SG, bool AFFINE, int RI, bool LOOP>
 __global__ __launch_bounds__(256, kGroupWavesPerEU) void sw_scan_lpt(LptParams prm) {
     using Elem = typename ix2::IntraImg<RI, true>::Elem;
     using PElem = typename ix2::IntraImg<2, true>::Elem;
-    constexpr size_t kInter = sizeof(X2pSmem<R, SG, 4>);
+    using Inter = X2pSmem<R, SG, 4, x2_col0<AFFINE, true>()>;
+    constexpr size_t kInter = sizeof(Inter);
     constexpr size_t kIntra = sizeof(Elem) * ix2::img_elems<RI, true>();
     constexpr size_t kPipe = kWavesPerWG * sizeof(PElem) * ix2::img_elems<2, true>() + kWavesPerWG * sizeof(int);
     constexpr size_t kDrain = drain_smem<AFFINE, RI>();
@@ -1329,8 +1386,7 @@ __global__ __launch_bounds__(256, kGroupWavesPerEU) void sw_scan_lpt(LptParams p
         const uint64_t t0 = trace_now();
         bool flagged;
         if (item >= 0)
-            flagged = x2p_wg<R, SG, AFFINE, true, true, 4>(a, item, a.blk_quad,
-                                                           *reinterpret_cast<X2pSmem<R, SG, 4>*>(smem));
+            flagged = x2p_wg<R, SG, AFFINE, true, true, 4>(a, item, a.blk_quad, *reinterpret_cast<Inter*>(smem));
         else if (-1 - item < niwg)
             flagged = ix2::intra_x2_wg<RI, true, false, !AFFINE, true, false, AFFINE, true>(
                 ia, -1 - item, reinterpret_cast<Elem*>(smem));

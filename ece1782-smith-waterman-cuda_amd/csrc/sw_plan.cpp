@@ -459,6 +459,13 @@ PlanScoring plan_scoring_pssm(const int8_t* rows, int32_t qlen, int go, int ge) 
 //    entries counted too.
 // Z = 0x2000 leaves both ends thousands away from kCellMin and kCellMax for
 // every admitted scheme over int8 entries.
+// The affine cell does not rebase H: column 0's diagonal sum takes the 8 ge
+// off through the hi0 image (hi - diff[1] mod 2^32, X2Lds in
+// sw_inter_x2.hip), so the sum d is the rebased form's bit for bit and H
+// keeps, across the sub-group boundary, the value it had just before the
+// rebase: no pattern is read that the rebased form did not read, and the two
+// bounds stand as they are.  diff[1], the dword 8 ge (2^16 + 1), is that
+// constant, also for open below extend.
 CellRange cell_range(int min_s, int max_s, int go, int ge) {
     CellRange c;
     c.z = 0x2000;
