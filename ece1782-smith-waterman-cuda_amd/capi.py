@@ -31,7 +31,7 @@ EXPORTED = (
     "sw_timing_reset", "sw_timing_total", "sw_stream_wait_scan", "sw_last_kernel", "sw_last_intra_kernel",
     "sw_topk", "sw_topk_device", "sw_topk_keys_device", "sw_topk_device_ids", "sw_scan_topk",
     "sw_scan_rank_device", "sw_score_pair",
-    "sw_align",
+    "sw_align", "sw_hit_stats", "sw_scan_hits",
     "sw_pssm_create", "sw_pssm_free", "sw_pssm_length", "sw_scan_pssm", "sw_scan_pssm_device",
     "sw_scan_pssm_topk", "sw_align_pssm",
     "sw_db_save", "sw_db_load", "sw_db_subjects", "sw_db_create_synthetic", "sw_synth_tables",
@@ -63,6 +63,25 @@ class DbStats(ctypes.Structure):
 class Alignment(ctypes.Structure):
     _fields_ = [("score", ctypes.c_int32), ("q_begin", ctypes.c_int32), ("q_end", ctypes.c_int32),
                 ("s_begin", ctypes.c_int32), ("s_end", ctypes.c_int32), ("ops_len", ctypes.c_int32)]
+
+
+class Hit(ctypes.Structure):
+    """sw_hit (include/sw_amd.h): one row of the hit table."""
+    FIELDS = ("id", "score", "q_begin", "q_end", "s_begin", "s_end", "s_len", "length", "identities", "positives",
+              "gap_opens", "gaps")
+    _fields_ = [(f, ctypes.c_int32) for f in FIELDS]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f in self.FIELDS}
+
+
+# The hit-table kernel's shape (csrc/sw_kernels.h kHitsRowsPerLane, kHitsWaves,
+# kHitsChunkRows): rows per thread, waves per hit, and the query rows per chunk
+# they make; a longer query hands its DP row from chunk to chunk through
+# device memory, a wave hands it to the next through LDS.
+HITS_ROWS_PER_LANE = 2
+HITS_WAVES = 4
+HITS_CHUNK_ROWS = 64 * HITS_WAVES * HITS_ROWS_PER_LANE
 
 
 class Opts(ctypes.Structure):
@@ -159,6 +178,8 @@ def lib():
         "sw_db_load": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.POINTER(vp)]),
         "sw_align": (ctypes.c_int, [vp, vp, u8p, i32, ctypes.POINTER(Scoring), i32p, i32,
                                     ctypes.POINTER(Alignment), ctypes.c_char_p, ctypes.c_int64]),
+        "sw_hit_stats": (ctypes.c_int, [vp, vp, u8p, i32, ctypes.POINTER(Scoring), i32p, i32, ctypes.POINTER(Hit)]),
+        "sw_scan_hits": (ctypes.c_int, [vp, vp, u8p, i32, ctypes.POINTER(Scoring), i32, ctypes.POINTER(Hit), i32p]),
         "sw_pssm_create": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int8), i32, ctypes.POINTER(vp)]),
         "sw_pssm_free": (ctypes.c_int, [vp]),
         "sw_pssm_length": (ctypes.c_int, [vp, i32p]),
@@ -568,6 +589,29 @@ class Database:
             res.append({"score": a.score, "q_begin": a.q_begin, "q_end": a.q_end, "s_begin": a.s_begin,
                         "s_end": a.s_end, "ops": buf.raw[k * stride: k * stride + a.ops_len].decode()})
         return res
+
+    def hit_stats(self, query_codes, ids, matrix=None, gap=2, gap_extend=None):
+        """The hit table's rows for the subjects with these result ids
+        (sw_hit_stats): the alignment align reports, as coordinates and counts
+        (no ops).  Returns a list of dicts with sw_hit's fields."""
+        q, qp = _u8(query_codes)
+        idv = np.ascontiguousarray(ids, dtype=np.int32)
+        n = len(idv)
+        sc = _ScoringArg(matrix, gap, gap if gap_extend is None else gap_extend)
+        out = (Hit * max(n, 1))()
+        _check(lib().sw_hit_stats(self.handle.ptr, self._d, qp, len(q), sc.ptr(),
+                                  idv.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n, out))
+        return [out[k].as_dict() for k in range(n)]
+
+    def scan_hits(self, query_codes, k, matrix=None, gap=2, gap_extend=None):
+        """A scan, its k best subjects (scan_topk's, in key order) and their
+        hit-table rows in one call (sw_scan_hits); min(k, subjects) dicts."""
+        q, qp = _u8(query_codes)
+        sc = _ScoringArg(matrix, gap, gap if gap_extend is None else gap_extend)
+        out = (Hit * max(int(k), 1))()
+        nhits = ctypes.c_int32(0)
+        _check(lib().sw_scan_hits(self.handle.ptr, self._d, qp, len(q), sc.ptr(), k, out, ctypes.byref(nhits)))
+        return [out[i].as_dict() for i in range(nhits.value)]
 
     def scan_pssm(self, pssm, gap_open=2, gap_extend=None):
         """Synchronous scan of a Pssm; int32 scores indexed by id (sw_scan_pssm)."""

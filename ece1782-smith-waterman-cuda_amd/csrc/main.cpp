@@ -26,6 +26,11 @@
 // meaning then and is an error).  The file and the flags are checked before
 // any GPU is touched.  Output: "Input profile: N positions", the id:score
 // lines, and the METRICS block with N as the query length.
+// Hit table: --hits K (1..4096) prints, in place of the id:score lines, one
+// tab-separated row per hit in rank order (sw_hit, sw_amd.h):
+//   id score q_begin q_end s_begin s_end s_len length identities positives gap_opens gaps
+// under the scoring flags, on one GPU; it cannot be combined with --pssm,
+// --topk or --gpus N > 1, and is checked before any file is read.
 #include <sys/time.h>
 
 #include <algorithm>
@@ -61,7 +66,9 @@ void usage() {
               << "  --matrix arg          blosum50 (default, the reference's), blosum62, or a matrix file\n"
               << "  --gap-open arg        Cost of a gap's first residue (default 2)\n"
               << "  --gap-extend arg      Cost of each further gap residue (default: --gap-open, linear)\n"
-              << "  --topk arg            Print only the arg best subjects (score desc, id asc)\n";
+              << "  --topk arg            Print only the arg best subjects (score desc, id asc)\n"
+              << "  --hits arg            Print the arg best subjects (1..4096) as a hit table: id score q_begin\n"
+              << "                        q_end s_begin s_end s_len length identities positives gap_opens gaps\n";
 }
 
 // a whole-string integer in [lo, hi]
@@ -94,11 +101,25 @@ int main(int argc, char* argv[]) {
             val = argv[++i];
         }
         if (key != "query" && key != "db" && key != "metrics-json" && key != "make-db" && key != "gpus" &&
-            key != "matrix" && key != "gap-open" && key != "gap-extend" && key != "topk" && key != "pssm") {
+            key != "matrix" && key != "gap-open" && key != "gap-extend" && key != "topk" && key != "pssm" && key != "hits") {
             std::cerr << "unrecognised option '--" << key << "'\n";
             return 1;
         }
         opt[key] = val;
+    }
+    int hits = 0;
+    if (opt.count("hits") && !help) {  // checked before any file is read
+        if (!parse_int(opt["hits"], 1, 4096, &hits)) {
+            std::cerr << "--hits must be an integer in 1..4096\n";
+            return 1;
+        }
+        const char* with = opt.count("pssm") ? "--pssm" : opt.count("topk") ? "--topk" : nullptr;
+        if (!with && opt.count("gpus") && std::atoi(opt["gpus"].c_str()) != 1) with = "--gpus N > 1";
+        if (!with && opt.count("make-db")) with = "--make-db";
+        if (with) {
+            std::cerr << "--hits cannot be combined with " << with << "\n";
+            return 1;
+        }
     }
     // reference: a missing required option prints the description and exits 1
     // (main.cpp:38-41), --help likewise (main.cpp:33-36)
@@ -182,6 +203,7 @@ int main(int argc, char* argv[]) {
 
     vector<seqid_score> result;
     result.reserve(600000);
+    std::vector<sw_hit> rows;  // --hits
     int64_t num_subjects = 0, length_sum = 0;
     double solve_s = 0, parse_s = 0;
     if (!binary) {
@@ -190,7 +212,8 @@ int main(int argc, char* argv[]) {
         parse_s = now_s() - t_parse;
         const double t_solve = now_s();
         try {
-            if (use_pssm) result = smith_waterman_cuda_pssm(prows, db, topk);
+            if (hits) rows = smith_waterman_cuda_hits(query, db, hits);
+            else if (use_pssm) result = smith_waterman_cuda_pssm(prows, db, topk);
             else if (topk) result = smith_waterman_cuda_topk(query, db, topk);
             else smith_waterman_cuda(query, db, result);
         } catch (const std::exception& e) {
@@ -218,8 +241,9 @@ int main(int argc, char* argv[]) {
         sw_db_subjects(sdb, lens.data(), ids.data());
         std::string q = query.get_buffer();
         // the reference pads the query (SWSolver.cu:267-269); its pad rows
-        // score 0 only under its own table (see swsolver.cpp encode_query)
-        while (!custom && q.size() % 8 != 0) q += "/";
+        // score 0 only under its own table (see swsolver.cpp encode_query);
+        // a hit table's coordinates are those of the query as written
+        while (!custom && !hits && q.size() % 8 != 0) q += "/";
         std::vector<uint8_t> qc(q.size());
         sw_encode(q.data(), static_cast<int64_t>(q.size()), qc.data());
         // BLOSUM50 (SWSolver.cu:54-81), gap 2 (:7), unless chosen
@@ -228,7 +252,13 @@ int main(int argc, char* argv[]) {
         if (use_pssm && sw_pssm_create(h, prows.data(), static_cast<int32_t>(prows.size() / 25), &pssm))
             return die("sw_pssm_create");
         const double t_solve = now_s();
-        if (topk && topk <= 4096) {
+        if (hits) {
+            rows.resize(static_cast<size_t>(hits));
+            int32_t nhits = 0;
+            if (sw_scan_hits(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, hits, rows.data(), &nhits))
+                return die("sw_scan_hits");
+            rows.resize(static_cast<size_t>(nhits));
+        } else if (topk && topk <= 4096) {
             std::vector<int64_t> keys(static_cast<size_t>(topk));
             if (use_pssm ? sw_scan_pssm_topk(h, sdb, pssm, gap_open, gap_extend, topk, keys.data())
                          : sw_scan_topk(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, topk, keys.data()))
@@ -274,6 +304,10 @@ int main(int argc, char* argv[]) {
 
     for (vector<seqid_score>::iterator it = result.begin(); it != result.end(); ++it)
         cout << (*it).first << ":" << (*it).second << "\n";
+    for (const sw_hit& r : rows)
+        cout << r.id << "\t" << r.score << "\t" << r.q_begin << "\t" << r.q_end << "\t" << r.s_begin << "\t" << r.s_end
+             << "\t" << r.s_len << "\t" << r.length << "\t" << r.identities << "\t" << r.positives << "\t"
+             << r.gap_opens << "\t" << r.gaps << "\n";
 
     const double seconds_elapsed = now_s() - time_start;
     cout << std::string(80, '=') << endl;

@@ -440,6 +440,10 @@ struct sw_db {
     std::vector<int64_t> h_offsets;
     std::vector<int32_t> h_ids;
     std::unordered_map<int32_t, int64_t> id_index;  // result id -> subject (built on first sw_align)
+    // subject -> its position in swpack::length_order (built on first
+    // sw_hit_stats: the layout's own order is released after upload); with the
+    // layout's nlong, swpack::locate gives where its residues are resident
+    std::vector<int64_t> pos_of;
     // synthetic database (sw_db_create_synthetic): residues are generated
     // on the device from (seed, id_base + local id); h_residues stays empty
     bool synthetic = false;
@@ -1803,7 +1807,7 @@ int topk_impl(sw_handle* h, const int32_t* scores, const int64_t* keys, int64_t 
 // ===========================================================================
 extern "C" {
 
-int32_t sw_version(void) { return 10000 * 0 + 100 * 2 + 0; }  // 0.2: sw_pssm_*
+int32_t sw_version(void) { return 10000 * 0 + 100 * 3 + 0; }  // 0.2: sw_pssm_*; 0.3: sw_hit_stats, sw_scan_hits
 
 #ifndef SW_SOURCE_ID
 #define SW_SOURCE_ID "unknown"
@@ -2516,9 +2520,115 @@ int align_impl(sw_handle* h, const sw_db* cdb, const QuerySrc& src, const int32_
     }
     return SW_OK;
 }
+
+// sw_hit_stats / sw_scan_hits: the rows of result ids[0..n) (sw_hits.hip).
+// What goes up: the query, the matrix and one descriptor per hit (where its
+// subject is resident); what comes down: the rows.
+int hits_impl(sw_handle* h, const sw_db* cdb, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
+              const int32_t* ids, int32_t n, sw_hit* out) {
+    sw_db* db = const_cast<sw_db*>(cdb);
+    if (!h || !db || n < 0 || qlen < 0 || (qlen > 0 && !query) || (n > 0 && (!ids || !out)))
+        return fail(SW_E_INVALID, "null argument");
+    const int8_t* mat = nullptr;
+    int go, ge, rc;
+    if ((rc = check_scoring(sc, &mat, &go, &ge))) return rc;
+    for (int32_t i = 0; i < qlen; ++i)
+        if (query[i] >= SW_ALPHABET) return fail(SW_E_INVALID, "query residue code out of range (use sw_encode)");
+    if (db->id_index.empty())
+        for (int64_t k = 0; k < db->n; ++k) db->id_index.emplace(db->h_ids[k], k);
+    if (db->pos_of.empty() && db->n > 0) {
+        const std::vector<int64_t> order = swpack::length_order(db->h_offsets.data(), db->n);
+        db->pos_of.resize(static_cast<size_t>(db->n));
+        for (int64_t p = 0; p < db->n; ++p) db->pos_of[order[p]] = p;
+    }
+    std::vector<swk::HitDesc> desc(static_cast<size_t>(n));
+    std::vector<int64_t> slens(static_cast<size_t>(n));
+    for (int32_t k = 0; k < n; ++k) {
+        auto it = db->id_index.find(ids[k]);
+        if (it == db->id_index.end()) return fail(SW_E_INVALID, "sw_hit_stats: id not in the database");
+        const int64_t subj = it->second;
+        const swpack::Location loc = swpack::locate(db->pos_of[subj], db->shape.nlong);
+        slens[k] = db->h_offsets[subj + 1] - db->h_offsets[subj];
+        if (qlen + slens[k] >= (int64_t(1) << 31)) return fail(SW_E_INVALID, "sw_hit_stats: qlen + subject length must be < 2^31");
+        desc[k] = swk::HitDesc{ids[k], static_cast<int32_t>(slens[k]), static_cast<int32_t>(loc.slot), loc.lane, 0};
+    }
+    for (int32_t k = 0; k < n; ++k) {
+        std::memset(&out[k], 0, sizeof(sw_hit));
+        out[k].id = ids[k];
+        out[k].s_len = desc[k].slen;
+    }
+    if (n == 0 || qlen == 0) return SW_OK;
+    HIPCHECK(hipSetDevice(h->device));
+    // groups of hits whose boundary rows fit the scratch budget; a group's rows start at column 0
+    const std::vector<int64_t> ends = swplan::hits_groups(qlen, slens.data(), n);
+    int64_t cols_max = 0;
+    for (size_t g = 0, k = 0; g < ends.size(); ++g) {
+        int64_t cols = 0;
+        for (; k < static_cast<size_t>(ends[g]); ++k) {
+            desc[k].scratch = cols;
+            cols += slens[k];
+        }
+        cols_max = std::max(cols_max, cols);
+    }
+    // one allocation: the query, the matrix, the descriptors, the rows (each 16-byte aligned)
+    const size_t qbytes = static_cast<size_t>(round_up(qlen, 16)), mbytes = 640;
+    const size_t dbytes = static_cast<size_t>(round_up(static_cast<int64_t>(desc.size() * sizeof(swk::HitDesc)), 16));
+    DevPtr<uint8_t> dq;
+    DevPtr<int32_t> dbnd;
+    HIPCHECK(swk::dev_alloc(dq, qbytes + mbytes + dbytes + static_cast<size_t>(n) * sizeof(sw_hit)));
+    swk::HitDesc* const ddesc = reinterpret_cast<swk::HitDesc*>(dq.get() + qbytes + mbytes);  // (aliases into dq)
+    sw_hit* const dout = reinterpret_cast<sw_hit*>(dq.get() + qbytes + mbytes + dbytes);
+    const int64_t bnd_bytes = swplan::hits_scratch_bytes(qlen, cols_max);
+    if (bnd_bytes) HIPCHECK(swk::dev_alloc(dbnd, static_cast<size_t>(bnd_bytes)));
+    hipStream_t const s = h->stream.get();
+    HIPCHECK(hipMemcpyAsync(dq.get(), query, qlen, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(dq.get() + qbytes, mat, 625, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(ddesc, desc.data(), desc.size() * sizeof(swk::HitDesc), hipMemcpyHostToDevice, s));
+    swk::HitArgs a{};
+    a.query = dq.get();
+    a.qlen = qlen;
+    a.mat = reinterpret_cast<const int8_t*>(dq.get() + qbytes);
+    a.gap_open = go;
+    a.gap_extend = ge;
+    a.res = db->lay.d_res.get();
+    a.blk_off = db->lay.d_blk_off.get();
+    a.lres = db->lay.d_lres.get();
+    a.loff = db->lay.d_loff.get();
+    a.bnd = dbnd.get();
+    int64_t k0 = 0;
+    for (const int64_t k1 : ends) {  // in stream order: the groups share the scratch
+        a.hits = ddesc + k0;
+        a.n = static_cast<int32_t>(k1 - k0);
+        a.out = dout + k0;
+        HIPCHECK(swk::launch_hits(a, s));
+        k0 = k1;
+    }
+    HIPCHECK(hipMemcpyAsync(out, dout, static_cast<size_t>(n) * sizeof(sw_hit), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    return SW_OK;
+}
 }  // namespace
 
 extern "C" {
+
+int sw_hit_stats(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
+                 const int32_t* ids, int32_t n, sw_hit* out) {
+    return hits_impl(h, db, query, qlen, sc, ids, n, out);
+}
+
+int sw_scan_hits(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc, int32_t k,
+                 sw_hit* out, int32_t* nhits) {
+    if (!h || !db || !out || !nhits || k <= 0 || k > 4096) return fail(SW_E_INVALID, "bad argument (1 <= k <= 4096)");
+    *nhits = 0;
+    std::vector<int64_t> keys(static_cast<size_t>(k));
+    if (int rc = scan_topk_host(h, db, seq_src(query, qlen, sc), k, keys.data())) return rc;
+    const int32_t m = static_cast<int32_t>(std::min<int64_t>(k, db->n));
+    std::vector<int32_t> ids(static_cast<size_t>(m));
+    for (int32_t i = 0; i < m; ++i) ids[i] = static_cast<int32_t>(0x7fffffff - (keys[i] & 0xffffffffll));
+    if (int rc = hits_impl(h, db, query, qlen, sc, ids.data(), m, out)) return rc;
+    *nhits = m;
+    return SW_OK;
+}
 
 int sw_align(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
              const int32_t* ids, int32_t n, sw_alignment* out, char* ops, int64_t ops_stride) {

@@ -382,6 +382,49 @@ struct AlignArgs {
 };
 hipError_t launch_align(const AlignArgs& a, hipStream_t s);
 
+// Hit table (sw_hits.hip, sw_hits_rules.h): one workgroup of kHitsWaves waves
+// per hit, each wave in sw_intra's shape, thread t owning kHitsRowsPerLane
+// query rows of a kHitsChunkRows-row chunk; each DP value carries its path's
+// begin cell and counters.
+constexpr int kHitsRowsPerLane = 2;
+constexpr int kHitsWaves = 4;
+constexpr int kHitsChunkRows = kLanes * kHitsWaves * kHitsRowsPerLane;
+// int32 words per subject column of a hit's chunk boundary row: the bottom
+// row's H (value + 7 path fields) and F (value + 6: its last op is known)
+constexpr int kHitsBndWords = 16;
+// Where a subject's residues are in the resident database: long slot `slot`
+// (lane < 0, d_lres at loff[slot]) or lane `lane` of inter block `slot`
+// (d_res at blk_off[slot]); swpack::locate gives it from the subject's
+// position in the length order.
+struct HitDesc {
+    int32_t id;       // result id (copied into the row)
+    int32_t slen;
+    int32_t slot;
+    int32_t lane;
+    int64_t scratch;  // first column of this hit's boundary row in HitArgs::bnd (unused when qlen <= kHitsChunkRows)
+};
+// Byte of residue j of a subject, from the start of its long slot or of its
+// block: the inter layout's groups of [64 lanes][16 codes], or plain bytes.
+__host__ __device__ constexpr uint64_t hit_residue_at(int lane, uint64_t j) {
+    return lane < 0 ? j : (j / kGroupCols) * kGroupBytes + static_cast<uint64_t>(lane) * kGroupCols + j % kGroupCols;
+}
+struct HitArgs {
+    const uint8_t* query;      // qlen residue codes
+    int32_t qlen;
+    const int8_t* mat;         // 25 x 25, code order
+    int32_t gap_open;
+    int32_t gap_extend;
+    const uint8_t* res;        // the database's inter part and its block offsets
+    const uint64_t* blk_off;
+    const uint8_t* lres;       // ... and its long part
+    const uint64_t* loff;
+    const HitDesc* hits;
+    int32_t n;
+    int32_t* bnd;              // boundary rows, kHitsBndWords int32 per column (null when qlen <= kHitsChunkRows)
+    sw_hit* out;               // n rows
+};
+hipError_t launch_hits(const HitArgs& a, hipStream_t s);
+
 // Synthetic databases generated on the device (sw_synth.hip).
 struct SynthFill {
     uint8_t* res;                // packed inter residues (layout of InterArgs)

@@ -101,6 +101,11 @@ Shape plan(const Subjects& s, int32_t long_threshold, bool want_lane_len) {
     return sh;
 }
 
+Location locate(int64_t p, int64_t nlong) {
+    if (p < nlong) return {p, -1};
+    return {(p - nlong) / swk::kLanes, static_cast<int32_t>((p - nlong) % swk::kLanes)};
+}
+
 // one block's bytes: [group][lane][16 codes], kPadCode past each subject
 void fill_block(const Subjects& s, const Shape& sh, int64_t b, uint8_t* dst) {
     std::memset(dst, swk::kPadCode, static_cast<size_t>(sh.blk_groups[b]) * swk::kGroupBytes);

@@ -58,6 +58,18 @@ struct Shape {
 
 Shape plan(const Subjects& s, int32_t long_threshold, bool want_lane_len);
 
+// Where the subject at position p of the length order (Shape::order[p]) lies
+// in a layout with nlong long subjects: long slot p (lane = -1), or lane
+// (p - nlong) % 64 of block (p - nlong) / 64.  Only nlong depends on the long
+// threshold, so a position survives a re-pack.  Residue j of the subject is
+// byte swk::hit_residue_at(lane, j) from loff[slot] / blk_off[slot]
+// (sw_hits.hip reads it there).
+struct Location {
+    int64_t slot;
+    int32_t lane;
+};
+Location locate(int64_t p, int64_t nlong);
+
 // Block b's bytes, all blk_groups[b] * kGroupBytes of them, padding included.
 void fill_block(const Subjects& s, const Shape& sh, int64_t b, uint8_t* dst);
 // Long subject k's bytes, all loff[k + 1] - loff[k] of them, padding included.

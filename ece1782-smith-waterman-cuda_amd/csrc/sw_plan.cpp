@@ -611,4 +611,25 @@ void ScanPlan::set_drain(bool got_rows) {
     kernel += "+drain";
 }
 
+int64_t hits_scratch_bytes(int32_t qlen, int64_t slen) {
+    if (qlen <= swk::kHitsChunkRows) return 0;
+    return slen * swk::kHitsBndWords * static_cast<int64_t>(sizeof(int32_t));
+}
+
+std::vector<int64_t> hits_groups(int32_t qlen, const int64_t* slens, int64_t n, int64_t budget) {
+    std::vector<int64_t> ends;
+    int64_t bytes = 0, k0 = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t b = hits_scratch_bytes(qlen, slens[k]);
+        if (k > k0 && bytes + b > budget) {
+            ends.push_back(k);
+            k0 = k;
+            bytes = 0;
+        }
+        bytes += b;
+    }
+    if (n > 0) ends.push_back(n);
+    return ends;
+}
+
 }  // namespace swplan

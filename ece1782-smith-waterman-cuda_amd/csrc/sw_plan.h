@@ -168,4 +168,15 @@ struct LptPlan {
 LptPlan lpt_plan(const PlanDb& db, int32_t qpad, int rows, int32_t qpad_intra, int ri, int32_t npair, int32_t nquad,
                  int32_t ntail, bool affine, bool tri);
 
+// The hit table's scratch (sw_hits.hip): a hit needs its chunk boundary row
+// only, swk::kHitsBndWords int32 per subject column, and only when the query
+// is longer than one chunk of swk::kHitsChunkRows rows; nothing grows with
+// qlen x slen.
+int64_t hits_scratch_bytes(int32_t qlen, int64_t slen);
+constexpr int64_t kHitsScratchBudget = int64_t(1) << 30;
+// Hits [ends[g - 1], ends[g]) (ends[-1] = 0) run as one launch: consecutive
+// hits whose scratch fits the budget; a single hit over the budget forms its
+// own group.  ends.back() == n; empty for n == 0.
+std::vector<int64_t> hits_groups(int32_t qlen, const int64_t* slens, int64_t n, int64_t budget = kHitsScratchBudget);
+
 }  // namespace swplan

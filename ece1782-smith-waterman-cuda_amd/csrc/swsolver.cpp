@@ -548,6 +548,38 @@ std::vector<seqid_score> smith_waterman_cuda_topk(FASTAQuery& query, FASTADataba
     return out;
 }
 
+std::vector<sw_hit> smith_waterman_cuda_hits(FASTAQuery& query, FASTADatabase& db, int k) {
+    if (k < 1 || k > 4096) throw std::invalid_argument("the hit table needs 1 <= k <= 4096");
+    std::lock_guard<std::mutex> lock(g_mu);
+    // coordinates are those of the sequences as written: no '/' padding of
+    // the subjects or the query (it scores 0 under the reference's table, so
+    // the scores are smith_waterman_cuda_topk's under any scoring)
+    const Flat f = timed_flatten(db, true);
+    const int64_t n = static_cast<int64_t>(f.record_ids.size());
+    for (int id : f.record_ids)
+        if (id < 0) throw std::invalid_argument("the hit table needs record ids (a FASTA header per subject)");
+    const std::vector<uint8_t> qc = encode_query(query, false);
+    const sw_scoring sc = {g_sc.has_matrix ? g_sc.mat : nullptr, g_sc.go, g_sc.ge};
+    std::vector<int32_t> ids(f.record_ids.begin(), f.record_ids.end());
+    std::vector<sw_hit> out(static_cast<size_t>(k));
+    g_timing.gpus = 1;
+    double t0 = now_s();
+    sw_handle* h = handle();
+    g_timing.init_s = now_s() - t0;
+    t0 = now_s();
+    sw_db* sdb = nullptr;
+    check(sw_db_create(h, f.residues.data(), f.offsets.data(), n, ids.data(), &sdb), "sw_db_create");
+    g_timing.upload_s = now_s() - t0;
+    t0 = now_s();
+    int32_t nhits = 0;
+    const int rc = sw_scan_hits(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, k, out.data(), &nhits);
+    g_timing.scan_s = now_s() - t0;
+    sw_db_free(sdb);
+    check(rc, "sw_scan_hits");
+    out.resize(static_cast<size_t>(nhits));
+    return out;
+}
+
 void smith_waterman_cuda(FASTAQuery& query, FASTADatabase& db, std::vector<seqid_score>& result) {
     std::lock_guard<std::mutex> lock(g_mu);  // the reference is not re-entrant either
     const Flat f = timed_flatten(db, g_sc.custom);

@@ -391,6 +391,46 @@ SW_API int sw_align(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t
                     const sw_scoring* sc, const int32_t* ids, int32_t n, sw_alignment* out,
                     char* ops, int64_t ops_stride);
 
+/* ---- hit table: coordinates and statistics without a traceback ------------
+ * One row per hit, what BLAST's tabular output or SSEARCH -m 8 prints (the
+ * reference prints id:score only, main.cpp:58-60): where the alignment lies
+ * in the query and in the subject, how long it is, its identities, positives
+ * and gaps.  The alignment is the one sw_align reports, under the same tie
+ * rules, linear and affine, and every field is a function of that
+ * alignment's begin cell, end cell and ops string — but no direction matrix
+ * is written and nothing is walked back: every column of the row is additive
+ * along the path, so each DP value carries its path's begin cell and
+ * counters forward (one wave per hit, memory O(|q| + |subject|), one pass).
+ * The subjects are read from the resident packed database: only hit
+ * descriptors go up and rows come down; a synthetic database regenerates
+ * nothing on the host.
+ *   sw_hit_stats : the rows of result ids[0..n), any n >= 0; an id the
+ *                  database does not hold is SW_E_INVALID.
+ *   sw_scan_hits : sw_scan_topk, then the rows of its ids in key order;
+ *                  1 <= k <= 4096, *nhits = min(k, subjects).  Synchronous.
+ * A hit of score 0, an empty subject or qlen == 0 reports 0 in every field
+ * but id and s_len (sw_align's 1 / 0 begin / end pair is not carried over).
+ * gap_opens counts maximal runs in the ops string, whatever the gap model
+ * (under linear gaps every gap residue is a DP opening; the count does not
+ * depend on that).  qlen + subject length < 2^31.  Arguments, error codes
+ * and faults as sw_align.
+ * Out of scope: the PSSM forms, sw_group_*, batches of queries, E-values and
+ * bit scores, and the ops string (that is sw_align's job).               */
+typedef struct sw_hit {
+    int32_t id, score;
+    int32_t q_begin, q_end, s_begin, s_end;   /* 1-based, inclusive, as sw_alignment */
+    int32_t s_len;                            /* the subject's length (coverage) */
+    int32_t length;                           /* alignment columns = sw_alignment.ops_len */
+    int32_t identities;                       /* M columns whose two residue codes are equal */
+    int32_t positives;                        /* M columns whose matrix entry is > 0 */
+    int32_t gap_opens;                        /* maximal runs of I or of D in the path (ID = two) */
+    int32_t gaps;                             /* I + D columns */
+} sw_hit;
+SW_API int sw_hit_stats(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen,
+                        const sw_scoring* sc, const int32_t* ids, int32_t n, sw_hit* out);
+SW_API int sw_scan_hits(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen,
+                        const sw_scoring* sc, int32_t k, sw_hit* out, int32_t* nhits);
+
 /* ---- profile (PSSM) queries ------------------------------------------------
  * A position-specific scoring matrix in the place of a query: a [qlen][25]
  * int8 table, rows[i*25 + c] = score of subject residue code c at query

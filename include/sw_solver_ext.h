@@ -65,6 +65,19 @@ bool sw_solver_read_matrix(const std::string& spec, int8_t out[625], std::string
  * the database is smaller.  k > 4096 ranks every score on the host. */
 std::vector<seqid_score> smith_waterman_cuda_topk(FASTAQuery& query, FASTADatabase& db, int k);
 
+/* The hit table (sw_amd.h sw_scan_hits; `main --hits K`): the k best subjects
+ * in smith_waterman_cuda_topk's order, each as a sw_hit row — the record id
+ * and score, where the alignment lies in the query and in the subject
+ * (1-based, inclusive), the subject's length, the alignment's length,
+ * identities, positives, gap runs and gap columns — under the scoring of
+ * sw_solver_set_scoring (default: the reference's).  Coordinates are those of
+ * the sequences as written: neither the subjects nor the query carry the '/'
+ * padding (it scores 0 under the reference's table, so the scores are the
+ * ranked scan's).  1 <= k <= 4096; fewer rows when the database is smaller.
+ * One GPU.  Throws std::invalid_argument for another k or a subject without
+ * a record id. */
+std::vector<sw_hit> smith_waterman_cuda_hits(FASTAQuery& query, FASTADatabase& db, int k);
+
 /* Profile (PSSM) queries (sw_amd.h sw_pssm_*; `main --pssm FILE`).
  * sw_solver_read_pssm reads a text PSSM into rows ([positions][25] int8 in
  * code order) and its consensus (one letter per position):
