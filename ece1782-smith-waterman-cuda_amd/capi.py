@@ -32,6 +32,7 @@ EXPORTED = (
     "sw_topk", "sw_topk_device", "sw_topk_keys_device", "sw_topk_device_ids", "sw_scan_topk",
     "sw_scan_rank_device", "sw_score_pair",
     "sw_align", "sw_hit_stats", "sw_scan_hits",
+    "sw_scan_batch_topk", "sw_hit_stats_batch", "sw_scan_batch_hits",
     "sw_pssm_create", "sw_pssm_free", "sw_pssm_length", "sw_scan_pssm", "sw_scan_pssm_device",
     "sw_scan_pssm_topk", "sw_align_pssm",
     "sw_db_save", "sw_db_load", "sw_db_subjects", "sw_db_create_synthetic", "sw_synth_tables",
@@ -180,6 +181,11 @@ def lib():
                                     ctypes.POINTER(Alignment), ctypes.c_char_p, ctypes.c_int64]),
         "sw_hit_stats": (ctypes.c_int, [vp, vp, u8p, i32, ctypes.POINTER(Scoring), i32p, i32, ctypes.POINTER(Hit)]),
         "sw_scan_hits": (ctypes.c_int, [vp, vp, u8p, i32, ctypes.POINTER(Scoring), i32, ctypes.POINTER(Hit), i32p]),
+        "sw_scan_batch_topk": (ctypes.c_int, [vp, vp, u8p, i64p, i32, ctypes.POINTER(Scoring), i32, i64p]),
+        "sw_hit_stats_batch": (ctypes.c_int, [vp, vp, u8p, i64p, i32, ctypes.POINTER(Scoring), i32p, i32p, i64,
+                                              ctypes.POINTER(Hit)]),
+        "sw_scan_batch_hits": (ctypes.c_int, [vp, vp, u8p, i64p, i32, ctypes.POINTER(Scoring), i32,
+                                              ctypes.POINTER(Hit), i32p]),
         "sw_pssm_create": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int8), i32, ctypes.POINTER(vp)]),
         "sw_pssm_free": (ctypes.c_int, [vp]),
         "sw_pssm_length": (ctypes.c_int, [vp, i32p]),
@@ -679,6 +685,51 @@ class Database:
                                    offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(queries),
                                    sc.ptr(), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
         return out
+
+    def scan_batch_topk(self, queries, k, matrix=None, gap_open=2, gap_extend=None):
+        """Every query's k best subjects as int64 keys [nq, k] (scan_topk's
+        keys; sw_scan_batch_topk: the scans back to back, each ranked on the
+        device, one copy and one synchronisation)."""
+        cat, offs = self._cat(queries)
+        c, cp = _u8(cat)
+        sc = _ScoringArg(matrix, gap_open, gap_extend)
+        out = np.zeros((len(queries), max(int(k), 0)), dtype=np.int64)
+        _check(lib().sw_scan_batch_topk(self.handle.ptr, self._d, cp,
+                                        offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(queries),
+                                        sc.ptr(), k, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return out
+
+    def hit_stats_batch(self, queries, pairs, matrix=None, gap=2, gap_extend=None):
+        """The hit table's rows of (query index, result id) pairs, in the
+        pairs' order (sw_hit_stats_batch: one launch sequence over all of
+        them).  Returns a list of dicts with sw_hit's fields."""
+        cat, offs = self._cat(queries)
+        c, cp = _u8(cat)
+        pv = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        qi, idv = np.ascontiguousarray(pv[:, 0]), np.ascontiguousarray(pv[:, 1])
+        n = len(pv)
+        sc = _ScoringArg(matrix, gap, gap if gap_extend is None else gap_extend)
+        out = (Hit * max(n, 1))()
+        _check(lib().sw_hit_stats_batch(self.handle.ptr, self._d, cp,
+                                        offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(queries), sc.ptr(),
+                                        qi.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                        idv.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n, out))
+        return [out[i].as_dict() for i in range(n)]
+
+    def scan_batch_hits(self, queries, k, matrix=None, gap=2, gap_extend=None):
+        """scan_hits for every query of a batch in one call (sw_scan_batch_hits:
+        two host synchronisations whatever the batch's size); a list of
+        len(queries) lists of min(k, subjects) dicts."""
+        cat, offs = self._cat(queries)
+        c, cp = _u8(cat)
+        sc = _ScoringArg(matrix, gap, gap if gap_extend is None else gap_extend)
+        nq, kk = len(queries), max(int(k), 1)
+        out = (Hit * max(nq * kk, 1))()
+        nhits = ctypes.c_int32(0)
+        _check(lib().sw_scan_batch_hits(self.handle.ptr, self._d, cp,
+                                        offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nq, sc.ptr(), k, out,
+                                        ctypes.byref(nhits)))
+        return [[out[q * kk + i].as_dict() for i in range(nhits.value)] for q in range(nq)]
 
 
 class Group:

@@ -31,6 +31,15 @@
 //   id score q_begin q_end s_begin s_end s_len length identities positives gap_opens gaps
 // under the scoring flags, on one GPU; it cannot be combined with --pssm,
 // --topk or --gpus N > 1, and is checked before any file is read.
+// Batches of queries: --queries FILE takes the place of --query: a FASTA file
+// of several records (sw_solver_read_queries), searched in one call of the
+// library (sw_scan_batch_hits / sw_scan_batch_topk) against a FASTA or a
+// .swdb database.  It needs --hits K or --topk K (1..4096) and cannot be
+// combined with --query, --pssm, --make-db or --gpus N > 1 (checked before
+// any file is read).  Output: "Input queries: N sequences, M residues"; per
+// query in file order a line "# query <index from 0> <name> <length>" and
+// its hit-table rows (--hits) or id:score lines (--topk); the METRICS block
+// with M as the query length, so its GCUPS count every query's cells.
 #include <sys/time.h>
 
 #include <algorithm>
@@ -60,6 +69,8 @@ void usage() {
               << "  --help                Display this help message\n"
               << "  --query arg           Path to query file (required, or --pssm)\n"
               << "  --pssm arg            Path to a PSSM text file, in the place of --query\n"
+              << "  --queries arg         Path to a multi-record FASTA file of queries, in the place of --query;\n"
+              << "                        needs --hits K or --topk K (1..4096): one block of output per query\n"
               << "  --db arg              Path to database file (required; FASTA, or a .swdb file)\n"
               << "  --make-db arg         Write the FASTA --db as a binary .swdb database and exit\n"
               << "  --gpus arg            Shard the FASTA database over this many GPUs (default 1)\n"
@@ -101,11 +112,28 @@ int main(int argc, char* argv[]) {
             val = argv[++i];
         }
         if (key != "query" && key != "db" && key != "metrics-json" && key != "make-db" && key != "gpus" &&
-            key != "matrix" && key != "gap-open" && key != "gap-extend" && key != "topk" && key != "pssm" && key != "hits") {
+            key != "matrix" && key != "gap-open" && key != "gap-extend" && key != "topk" && key != "pssm" && key != "hits" &&
+            key != "queries") {
             std::cerr << "unrecognised option '--" << key << "'\n";
             return 1;
         }
         opt[key] = val;
+    }
+    const bool use_queries = opt.count("queries") != 0;
+    if (use_queries && !help) {  // checked before any file is read
+        const char* with = opt.count("query") ? "--query" : opt.count("pssm") ? "--pssm" : nullptr;
+        if (!with && opt.count("make-db")) with = "--make-db";
+        if (!with && opt.count("gpus") && std::atoi(opt["gpus"].c_str()) != 1) with = "--gpus N > 1";
+        if (with) {
+            std::cerr << "--queries cannot be combined with " << with << "\n";
+            return 1;
+        }
+        int k = 0;
+        if (opt.count("hits") + opt.count("topk") != 1 ||
+            !parse_int(opt.count("hits") ? opt["hits"] : opt["topk"], 1, 4096, &k)) {
+            std::cerr << "--queries needs --hits K or --topk K, K an integer in 1..4096\n";
+            return 1;
+        }
     }
     int hits = 0;
     if (opt.count("hits") && !help) {  // checked before any file is read
@@ -136,7 +164,7 @@ int main(int argc, char* argv[]) {
         return 0;
     }
     const bool use_pssm = opt.count("pssm") != 0;
-    if (opt.count("query") + opt.count("pssm") != 1 || !opt.count("db") || help || argc <= 1) {
+    if (opt.count("query") + opt.count("pssm") + opt.count("queries") != 1 || !opt.count("db") || help || argc <= 1) {
         if (opt.count("query") && use_pssm) std::cerr << "--pssm takes the place of --query: give one of the two\n";
         usage();
         return 1;
@@ -190,20 +218,36 @@ int main(int argc, char* argv[]) {
             return 1;
         }
     }
-    FASTAQuery query(use_pssm ? std::string() : opt["query"], true);  // (no file: an empty buffer)
+    std::vector<std::string> qnames, qseqs;  // --queries
+    size_t qresidues = 0;
+    if (use_queries) {
+        std::string err;
+        if (!sw_solver_read_queries(opt["queries"], &qnames, &qseqs, &err)) {
+            std::cerr << "--queries " << err << "\n";
+            return 1;
+        }
+        for (const std::string& s : qseqs) qresidues += s.size();
+    }
+    FASTAQuery query(use_pssm || use_queries ? std::string() : opt["query"], true);  // (no file: an empty buffer)
     if (use_pssm) {
         cout << "Input profile: " << prows.size() / 25 << " positions" << endl;
+    } else if (use_queries) {
+        cout << "Input queries: " << qseqs.size() << " sequences, " << qresidues << " residues" << endl;
     } else {
         cout << "Input buffer:";
         query.print_buffer();
         cout << endl;
     }
-    // the query length of the METRICS block: the PSSM's positions
-    const string querySequence = use_pssm ? string(prows.size() / 25, 'X') : query.get_buffer();
+    // the query length of the METRICS block: the PSSM's positions, a batch's residues
+    const string querySequence = use_pssm      ? string(prows.size() / 25, 'X')
+                                 : use_queries ? string(qresidues, 'X')
+                                               : query.get_buffer();
 
     vector<seqid_score> result;
-    result.reserve(600000);
+    result.reserve(use_queries ? 0 : 600000);
     std::vector<sw_hit> rows;  // --hits
+    std::vector<std::vector<seqid_score> > bresult;  // --queries: one block per query
+    std::vector<std::vector<sw_hit> > brows;
     int64_t num_subjects = 0, length_sum = 0;
     double solve_s = 0, parse_s = 0;
     if (!binary) {
@@ -212,7 +256,9 @@ int main(int argc, char* argv[]) {
         parse_s = now_s() - t_parse;
         const double t_solve = now_s();
         try {
-            if (hits) rows = smith_waterman_cuda_hits(query, db, hits);
+            if (use_queries && hits) brows = smith_waterman_cuda_batch_hits(qseqs, db, hits);
+            else if (use_queries) bresult = smith_waterman_cuda_batch_topk(qseqs, db, topk);
+            else if (hits) rows = smith_waterman_cuda_hits(query, db, hits);
             else if (use_pssm) result = smith_waterman_cuda_pssm(prows, db, topk);
             else if (topk) result = smith_waterman_cuda_topk(query, db, topk);
             else smith_waterman_cuda(query, db, result);
@@ -252,7 +298,36 @@ int main(int argc, char* argv[]) {
         if (use_pssm && sw_pssm_create(h, prows.data(), static_cast<int32_t>(prows.size() / 25), &pssm))
             return die("sw_pssm_create");
         const double t_solve = now_s();
-        if (hits) {
+        if (use_queries) {
+            // the queries as written, concatenated (sw_scan_batch's form)
+            const int32_t nq = static_cast<int32_t>(qseqs.size());
+            std::vector<int64_t> qoffs(qseqs.size() + 1, 0);
+            for (size_t i = 0; i < qseqs.size(); ++i) qoffs[i + 1] = qoffs[i] + static_cast<int64_t>(qseqs[i].size());
+            std::vector<uint8_t> cat(qresidues);
+            for (size_t i = 0; i < qseqs.size(); ++i)
+                sw_encode(qseqs[i].data(), static_cast<int64_t>(qseqs[i].size()), cat.data() + qoffs[i]);
+            if (hits) {
+                std::vector<sw_hit> all(qseqs.size() * static_cast<size_t>(hits));
+                int32_t nhits = 0;
+                if (sw_scan_batch_hits(h, sdb, cat.data(), qoffs.data(), nq, &sc, hits, all.data(), &nhits))
+                    return die("sw_scan_batch_hits");
+                for (size_t i = 0; i < qseqs.size(); ++i)
+                    brows.push_back(std::vector<sw_hit>(all.begin() + static_cast<int64_t>(i) * hits,
+                                                        all.begin() + static_cast<int64_t>(i) * hits + nhits));
+            } else {
+                std::vector<int64_t> keys(qseqs.size() * static_cast<size_t>(topk));
+                if (sw_scan_batch_topk(h, sdb, cat.data(), qoffs.data(), nq, &sc, topk, keys.data()))
+                    return die("sw_scan_batch_topk");
+                bresult.resize(qseqs.size());
+                for (size_t i = 0; i < qseqs.size(); ++i)
+                    for (int j = 0; j < topk; ++j) {
+                        const int64_t key = keys[i * static_cast<size_t>(topk) + j];
+                        if (key == INT64_MIN) break;
+                        bresult[i].push_back(std::make_pair(static_cast<int>((int64_t{1} << 31) - 1 - (key & 0xffffffff)),
+                                                            static_cast<int>(key >> 32)));
+                    }
+            }
+        } else if (hits) {
             rows.resize(static_cast<size_t>(hits));
             int32_t nhits = 0;
             if (sw_scan_hits(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, hits, rows.data(), &nhits))
@@ -302,12 +377,24 @@ int main(int argc, char* argv[]) {
         sw_destroy(h);
     }
 
-    for (vector<seqid_score>::iterator it = result.begin(); it != result.end(); ++it)
-        cout << (*it).first << ":" << (*it).second << "\n";
-    for (const sw_hit& r : rows)
-        cout << r.id << "\t" << r.score << "\t" << r.q_begin << "\t" << r.q_end << "\t" << r.s_begin << "\t" << r.s_end
-             << "\t" << r.s_len << "\t" << r.length << "\t" << r.identities << "\t" << r.positives << "\t"
-             << r.gap_opens << "\t" << r.gaps << "\n";
+    auto print_scores = [](const vector<seqid_score>& v) {
+        for (vector<seqid_score>::const_iterator it = v.begin(); it != v.end(); ++it)
+            cout << (*it).first << ":" << (*it).second << "\n";
+    };
+    auto print_rows = [](const std::vector<sw_hit>& v) {
+        for (const sw_hit& r : v)
+            cout << r.id << "\t" << r.score << "\t" << r.q_begin << "\t" << r.q_end << "\t" << r.s_begin << "\t"
+                 << r.s_end << "\t" << r.s_len << "\t" << r.length << "\t" << r.identities << "\t" << r.positives
+                 << "\t" << r.gap_opens << "\t" << r.gaps << "\n";
+    };
+    print_scores(result);
+    print_rows(rows);
+    // --queries: a block per query, in file order (index from 0; "-" for a header without a name)
+    for (size_t i = 0; i < qseqs.size(); ++i) {
+        cout << "# query " << i << " " << (qnames[i].empty() ? "-" : qnames[i]) << " " << qseqs[i].size() << "\n";
+        if (i < brows.size()) print_rows(brows[i]);
+        if (i < bresult.size()) print_scores(bresult[i]);
+    }
 
     const double seconds_elapsed = now_s() - time_start;
     cout << std::string(80, '=') << endl;

@@ -1807,7 +1807,7 @@ int topk_impl(sw_handle* h, const int32_t* scores, const int64_t* keys, int64_t 
 // ===========================================================================
 extern "C" {
 
-int32_t sw_version(void) { return 10000 * 0 + 100 * 3 + 0; }  // 0.2: sw_pssm_*; 0.3: sw_hit_stats, sw_scan_hits
+int32_t sw_version(void) { return 10000 * 0 + 100 * 4 + 0; }  // 0.2: sw_pssm_*; 0.3: sw_hit_stats, sw_scan_hits; 0.4: sw_scan_batch_topk, sw_*_hits batch forms
 
 #ifndef SW_SOURCE_ID
 #define SW_SOURCE_ID "unknown"
@@ -2521,19 +2521,30 @@ int align_impl(sw_handle* h, const sw_db* cdb, const QuerySrc& src, const int32_
     return SW_OK;
 }
 
-// sw_hit_stats / sw_scan_hits: the rows of result ids[0..n) (sw_hits.hip).
-// What goes up: the query, the matrix and one descriptor per hit (where its
-// subject is resident); what comes down: the rows.
-int hits_impl(sw_handle* h, const sw_db* cdb, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
-              const int32_t* ids, int32_t n, sw_hit* out) {
+// The hit table (sw_hits.hip): the rows of the pairs (query qidx[k], result
+// id ids[k]), k in [0, n), into out[k]; qidx null: every pair is query 0's
+// (sw_hit_stats, sw_scan_hits).  The queries are those of a batch
+// (check_batch has passed).  What goes up, once: the queries, the matrix and
+// one descriptor per hit (its query, where its subject is resident, its row);
+// what comes down, once: the rows.  The hits launch in swplan::hits_order's
+// order, longest wavefront first, in groups whose boundary rows fit the
+// scratch budget; one synchronisation ends the call.
+int hits_impl(sw_handle* h, const sw_db* cdb, const uint8_t* queries, const int64_t* qoffsets, int32_t nq,
+              const sw_scoring* sc, const int32_t* qidx, const int32_t* ids, int64_t n, sw_hit* out) {
     sw_db* db = const_cast<sw_db*>(cdb);
-    if (!h || !db || n < 0 || qlen < 0 || (qlen > 0 && !query) || (n > 0 && (!ids || !out)))
+    if (!h || !db || n < 0 || n >= (int64_t(1) << 31) || nq < 0 || (nq > 0 && !qoffsets) || (n > 0 && (!ids || !out)))
         return fail(SW_E_INVALID, "null argument");
+    const int64_t qbase = nq > 0 ? qoffsets[0] : 0, qtotal = nq > 0 ? qoffsets[nq] - qbase : 0;
+    if (qtotal > 0 && !queries) return fail(SW_E_INVALID, "null argument");
     const int8_t* mat = nullptr;
     int go, ge, rc;
     if ((rc = check_scoring(sc, &mat, &go, &ge))) return rc;
-    for (int32_t i = 0; i < qlen; ++i)
-        if (query[i] >= SW_ALPHABET) return fail(SW_E_INVALID, "query residue code out of range (use sw_encode)");
+    for (int64_t i = 0; i < qtotal; ++i)
+        if (queries[qbase + i] >= SW_ALPHABET) return fail(SW_E_INVALID, "query residue code out of range (use sw_encode)");
+    for (int64_t k = 0; k < n; ++k) {
+        const int32_t qi = qidx ? qidx[k] : 0;
+        if (qi < 0 || qi >= nq) return fail(SW_E_INVALID, "sw_hit_stats_batch: query index outside [0, nq)");
+    }
     if (db->id_index.empty())
         for (int64_t k = 0; k < db->n; ++k) db->id_index.emplace(db->h_ids[k], k);
     if (db->pos_of.empty() && db->n > 0) {
@@ -2541,52 +2552,72 @@ int hits_impl(sw_handle* h, const sw_db* cdb, const uint8_t* query, int32_t qlen
         db->pos_of.resize(static_cast<size_t>(db->n));
         for (int64_t p = 0; p < db->n; ++p) db->pos_of[order[p]] = p;
     }
-    std::vector<swk::HitDesc> desc(static_cast<size_t>(n));
+    // per pair, in the caller's order: the lengths, and the row as the host knows it
+    std::vector<swk::HitDesc> hit(static_cast<size_t>(n));
+    std::vector<int32_t> qlens(static_cast<size_t>(n));
     std::vector<int64_t> slens(static_cast<size_t>(n));
-    for (int32_t k = 0; k < n; ++k) {
+    int64_t work = 0;
+    for (int64_t k = 0; k < n; ++k) {
         auto it = db->id_index.find(ids[k]);
         if (it == db->id_index.end()) return fail(SW_E_INVALID, "sw_hit_stats: id not in the database");
         const int64_t subj = it->second;
+        const int32_t qi = qidx ? qidx[k] : 0;
         const swpack::Location loc = swpack::locate(db->pos_of[subj], db->shape.nlong);
+        qlens[k] = static_cast<int32_t>(qoffsets[qi + 1] - qoffsets[qi]);
         slens[k] = db->h_offsets[subj + 1] - db->h_offsets[subj];
-        if (qlen + slens[k] >= (int64_t(1) << 31)) return fail(SW_E_INVALID, "sw_hit_stats: qlen + subject length must be < 2^31");
-        desc[k] = swk::HitDesc{ids[k], static_cast<int32_t>(slens[k]), static_cast<int32_t>(loc.slot), loc.lane, 0};
+        if (qlens[k] + slens[k] >= (int64_t(1) << 31)) return fail(SW_E_INVALID, "sw_hit_stats: qlen + subject length must be < 2^31");
+        hit[k] = swk::HitDesc{ids[k], static_cast<int32_t>(slens[k]), static_cast<int32_t>(loc.slot), loc.lane, 0,
+                              qoffsets[qi] - qbase, qlens[k], static_cast<int32_t>(k)};
+        work += swplan::hits_cost(qlens[k], slens[k]);
     }
-    for (int32_t k = 0; k < n; ++k) {
+    for (int64_t k = 0; k < n; ++k) {
         std::memset(&out[k], 0, sizeof(sw_hit));
         out[k].id = ids[k];
-        out[k].s_len = desc[k].slen;
+        out[k].s_len = hit[k].slen;
     }
-    if (n == 0 || qlen == 0) return SW_OK;
+    if (work == 0) return SW_OK;  // no pair has a cell: every row is the zero row above
     HIPCHECK(hipSetDevice(h->device));
-    // groups of hits whose boundary rows fit the scratch budget; a group's rows start at column 0
-    const std::vector<int64_t> ends = swplan::hits_groups(qlen, slens.data(), n);
+    // the launch order; then groups of hits, in that order, whose boundary
+    // rows fit the scratch budget.  A group's rows start at column 0, and every
+    // multi-chunk hit has its own (two queries may hit one subject).
+    const std::vector<int64_t> order = swplan::hits_order(qlens.data(), slens.data(), n);
+    std::vector<swk::HitDesc> desc(static_cast<size_t>(n));
+    std::vector<int32_t> oq(static_cast<size_t>(n));
+    std::vector<int64_t> os(static_cast<size_t>(n));
+    for (int64_t k = 0; k < n; ++k) {
+        desc[k] = hit[order[k]];
+        oq[k] = qlens[order[k]];
+        os[k] = slens[order[k]];
+    }
+    const std::vector<int64_t> ends = swplan::hits_groups(oq.data(), os.data(), n);
     int64_t cols_max = 0;
+    int32_t qlen_max = 0;
     for (size_t g = 0, k = 0; g < ends.size(); ++g) {
         int64_t cols = 0;
         for (; k < static_cast<size_t>(ends[g]); ++k) {
             desc[k].scratch = cols;
-            cols += slens[k];
+            if (oq[k] > swk::kHitsChunkRows) cols += os[k];
+            if (os[k] > 0) qlen_max = std::max(qlen_max, oq[k]);  // (an empty subject's workgroup returns at once)
         }
         cols_max = std::max(cols_max, cols);
     }
-    // one allocation: the query, the matrix, the descriptors, the rows (each 16-byte aligned)
-    const size_t qbytes = static_cast<size_t>(round_up(qlen, 16)), mbytes = 640;
+    // one allocation: the queries, the matrix, the descriptors, the rows (each 16-byte aligned)
+    const size_t qbytes = static_cast<size_t>(round_up(qtotal, 16)), mbytes = 640;
     const size_t dbytes = static_cast<size_t>(round_up(static_cast<int64_t>(desc.size() * sizeof(swk::HitDesc)), 16));
     DevPtr<uint8_t> dq;
     DevPtr<int32_t> dbnd;
     HIPCHECK(swk::dev_alloc(dq, qbytes + mbytes + dbytes + static_cast<size_t>(n) * sizeof(sw_hit)));
     swk::HitDesc* const ddesc = reinterpret_cast<swk::HitDesc*>(dq.get() + qbytes + mbytes);  // (aliases into dq)
     sw_hit* const dout = reinterpret_cast<sw_hit*>(dq.get() + qbytes + mbytes + dbytes);
-    const int64_t bnd_bytes = swplan::hits_scratch_bytes(qlen, cols_max);
+    const int64_t bnd_bytes = swplan::hits_scratch_bytes(qlen_max, cols_max);
     if (bnd_bytes) HIPCHECK(swk::dev_alloc(dbnd, static_cast<size_t>(bnd_bytes)));
     hipStream_t const s = h->stream.get();
-    HIPCHECK(hipMemcpyAsync(dq.get(), query, qlen, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(dq.get(), queries + qbase, static_cast<size_t>(qtotal), hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(dq.get() + qbytes, mat, 625, hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(ddesc, desc.data(), desc.size() * sizeof(swk::HitDesc), hipMemcpyHostToDevice, s));
     swk::HitArgs a{};
     a.query = dq.get();
-    a.qlen = qlen;
+    a.qlen_max = qlen_max;
     a.mat = reinterpret_cast<const int8_t*>(dq.get() + qbytes);
     a.gap_open = go;
     a.gap_extend = ge;
@@ -2595,17 +2626,65 @@ int hits_impl(sw_handle* h, const sw_db* cdb, const uint8_t* query, int32_t qlen
     a.lres = db->lay.d_lres.get();
     a.loff = db->lay.d_loff.get();
     a.bnd = dbnd.get();
+    a.out = dout;  // a hit writes its own row (HitDesc::row): the caller's order
     int64_t k0 = 0;
     for (const int64_t k1 : ends) {  // in stream order: the groups share the scratch
         a.hits = ddesc + k0;
         a.n = static_cast<int32_t>(k1 - k0);
-        a.out = dout + k0;
         HIPCHECK(swk::launch_hits(a, s));
         k0 = k1;
     }
     HIPCHECK(hipMemcpyAsync(out, dout, static_cast<size_t>(n) * sizeof(sw_hit), hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
     return SW_OK;
+}
+
+// One query as a batch of one (sw_hit_stats, sw_scan_hits).
+int hits_impl(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
+              const int32_t* ids, int32_t n, sw_hit* out) {
+    if (qlen < 0 || (qlen > 0 && !query)) return fail(SW_E_INVALID, "null argument");
+    const int64_t offs[2] = {0, qlen};
+    return hits_impl(h, db, query, offs, 1, sc, nullptr, ids, n, out);
+}
+
+// The batch's argument checks, shared by the three batch calls below.
+int check_batch_args(sw_handle* h, const sw_db* db, const uint8_t* queries, const int64_t* qoffsets, int32_t nq) {
+    if (!h || !db || nq < 0 || (nq > 0 && !qoffsets)) return fail(SW_E_INVALID, "null argument");
+    if (int rc = check_batch(qoffsets, nq)) return rc;
+    if (nq > 0 && qoffsets[nq] > qoffsets[0] && !queries) return fail(SW_E_INVALID, "null argument");
+    return SW_OK;
+}
+
+// sw_scan_batch_topk: the scans back to back on the handle's stream, each
+// with its ranking (RankReq: the top-K follows every stage that writes that
+// query's scores, its rescue tail included, and the next scan's writes follow
+// it in stream order), into keys[nq][k] behind ONE score row; one copy and
+// one synchronisation end the call.
+int batch_topk_impl(sw_handle* h, const sw_db* cdb, const uint8_t* queries, const int64_t* qoffsets, int32_t nq,
+                    const sw_scoring* sc, int32_t k, int64_t* keys_host) {
+    sw_db* db = const_cast<sw_db*>(cdb);
+    int rc;
+    if ((rc = check_batch_args(h, db, queries, qoffsets, nq))) return rc;
+    if (k <= 0 || k > 4096 || (nq > 0 && !keys_host)) return fail(SW_E_INVALID, "bad argument (1 <= k <= 4096)");
+    if (nq == 0) return SW_OK;
+    const size_t nkeys = static_cast<size_t>(nq) * static_cast<size_t>(k);
+    if (db->n == 0) {
+        for (size_t i = 0; i < nkeys; ++i) keys_host[i] = INT64_MIN;
+        return SW_OK;
+    }
+    HIPCHECK(hipSetDevice(h->device));
+    const size_t slots = static_cast<size_t>(db->max_id + 1);
+    if ((rc = ensure_scores(h, slots + 2 * nkeys + 2))) return rc;  // the score row, then the nq x k keys
+    int64_t* keys_dev = reinterpret_cast<int64_t*>(h->d_scores.get() + round_up(static_cast<int64_t>(slots), 2));
+    for (int32_t q = 0; q < nq; ++q) {
+        const RankReq rq{k, nullptr, 0, keys_dev + static_cast<size_t>(q) * k};
+        if ((rc = scan_impl(h, db, queries + qoffsets[q], static_cast<int32_t>(qoffsets[q + 1] - qoffsets[q]), sc,
+                            h->d_scores.get(), false, &rq)))
+            return rc;
+    }
+    HIPCHECK(hipMemcpyAsync(keys_host, keys_dev, nkeys * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream.get()));
+    HIPCHECK(hipStreamSynchronize(h->stream.get()));
+    return check_fault(h);
 }
 }  // namespace
 
@@ -2614,6 +2693,50 @@ extern "C" {
 int sw_hit_stats(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
                  const int32_t* ids, int32_t n, sw_hit* out) {
     return hits_impl(h, db, query, qlen, sc, ids, n, out);
+}
+
+int sw_scan_batch_topk(sw_handle* h, const sw_db* db, const uint8_t* queries, const int64_t* qoffsets, int32_t nq,
+                       const sw_scoring* sc, int32_t k, int64_t* keys_host) {
+    return batch_topk_impl(h, db, queries, qoffsets, nq, sc, k, keys_host);
+}
+
+int sw_hit_stats_batch(sw_handle* h, const sw_db* db, const uint8_t* queries, const int64_t* qoffsets, int32_t nq,
+                       const sw_scoring* sc, const int32_t* qidx, const int32_t* ids, int64_t n, sw_hit* out) {
+    int rc;
+    if ((rc = check_batch_args(h, db, queries, qoffsets, nq))) return rc;
+    if (n < 0 || n >= (int64_t(1) << 31) || (n > 0 && (!qidx || !ids || !out)))
+        return fail(SW_E_INVALID, "bad argument (0 <= n < 2^31)");
+    if ((rc = hits_impl(h, db, queries, qoffsets, nq, sc, qidx, ids, n, out))) return rc;
+    return check_fault(h);
+}
+
+int sw_scan_batch_hits(sw_handle* h, const sw_db* db, const uint8_t* queries, const int64_t* qoffsets, int32_t nq,
+                       const sw_scoring* sc, int32_t k, sw_hit* out, int32_t* nhits) {
+    if (!h || !db || !nhits || k <= 0 || k > 4096 || (nq > 0 && !out))
+        return fail(SW_E_INVALID, "bad argument (1 <= k <= 4096)");
+    *nhits = 0;
+    int rc;
+    if ((rc = check_batch_args(h, db, queries, qoffsets, nq))) return rc;
+    // first synchronisation: every query's keys
+    std::vector<int64_t> keys(static_cast<size_t>(std::max(nq, 0)) * static_cast<size_t>(k));
+    if ((rc = batch_topk_impl(h, db, queries, qoffsets, nq, sc, k, keys.data()))) return rc;
+    const int32_t m = static_cast<int32_t>(std::min<int64_t>(k, db->n));
+    // second: the rows of all nq x m pairs, one launch sequence
+    const size_t np = static_cast<size_t>(nq) * static_cast<size_t>(m);
+    std::vector<int32_t> qidx(np), ids(np);
+    std::vector<sw_hit> rows(np);
+    for (int32_t q = 0; q < nq; ++q)
+        for (int32_t i = 0; i < m; ++i) {
+            qidx[static_cast<size_t>(q) * m + i] = q;
+            ids[static_cast<size_t>(q) * m + i] =
+                static_cast<int32_t>(0x7fffffff - (keys[static_cast<size_t>(q) * k + i] & 0xffffffffll));
+        }
+    if ((rc = hits_impl(h, db, queries, qoffsets, nq, sc, qidx.data(), ids.data(), static_cast<int64_t>(np), rows.data())))
+        return rc;
+    for (int32_t q = 0; q < nq && m > 0; ++q)
+        std::memcpy(out + static_cast<size_t>(q) * k, rows.data() + static_cast<size_t>(q) * m, static_cast<size_t>(m) * sizeof(sw_hit));
+    *nhits = m;
+    return check_fault(h);
 }
 
 int sw_scan_hits(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc, int32_t k,

@@ -20,6 +20,11 @@
 // columns ascend, so on equal values only a smaller row wins), and the
 // workgroup reduces (value, row, column).
 //
+// A hit is a (query, subject) pair (HitDesc): one launch may mix queries of
+// any lengths (sw_hit_stats_batch), one-chunk hits, which never touch the
+// scratch, beside multi-chunk ones, and empty queries; the host orders the
+// grid (swplan::hits_order) and each hit writes the row its descriptor names.
+//
 // The subject is read where the scan kernels read it, in the resident packed
 // database (HitDesc, hit_residue_at): no residue is uploaded.  Codes there
 // are stored codes (kStored), so the per-chunk LDS profile is built in stored
@@ -82,8 +87,12 @@ __global__ __launch_bounds__(kLanes * W) void sw_hits(HitArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid / kLanes);
     const int hit = static_cast<int>(blockIdx.x);
     const HitDesc d = a.hits[hit];
-    const int L = d.slen, qlen = a.qlen;
-    sw_hit* const o = a.out + hit;
+    // the query is the hit's own: everything below that depends on it (the
+    // chunk loop, wact, first / last, the padding rows, the profile, whether
+    // bnd is touched) follows d.qlen, uniform over the workgroup
+    const int L = d.slen, qlen = d.qlen;
+    const uint8_t* __restrict__ query = a.query + d.qoff;
+    sw_hit* const o = a.out + d.row;
     if (tid == 0) {
         o->id = d.id;
         o->s_len = d.slen;
@@ -113,7 +122,7 @@ __global__ __launch_bounds__(kLanes * W) void sw_hits(HitArgs a) {
 #pragma unroll
         for (int r = 0; r < RI; ++r) {
             const int row = row1 - 1 + r;
-            const int qc = row < qlen ? a.query[row] : 255;
+            const int qc = row < qlen ? query[row] : 255;
             qst[r] = qc < kAlphabet ? kStored[qc] : 255;
             for (int c = 0; c < NCODE; ++c)
                 prof[c * S + tid * RIP + r] =
@@ -271,7 +280,7 @@ __global__ __launch_bounds__(kLanes * W) void sw_hits(HitArgs a) {
 
 hipError_t launch_hits(const HitArgs& a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
-    if (a.qlen > kHitsChunkRows && !a.bnd) return hipErrorInvalidValue;
+    if (a.qlen_max > kHitsChunkRows && !a.bnd) return hipErrorInvalidValue;
     hipLaunchKernelGGL((sw_hits<kHitsRowsPerLane, kHitsWaves>), dim3(a.n), dim3(kLanes * kHitsWaves), 0, s, a);
     return hipGetLastError();
 }

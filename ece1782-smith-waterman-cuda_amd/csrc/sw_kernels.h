@@ -396,12 +396,18 @@ constexpr int kHitsBndWords = 16;
 // (lane < 0, d_lres at loff[slot]) or lane `lane` of inter block `slot`
 // (d_res at blk_off[slot]); swpack::locate gives it from the subject's
 // position in the length order.
+// A hit is a (query, subject) pair: a launch may mix queries (sw_hit_stats_batch),
+// so the query is the hit's own, a span of HitArgs::query, and so is the row it
+// writes, which leaves the grid's order to the host (swplan::hits_order).
 struct HitDesc {
     int32_t id;       // result id (copied into the row)
     int32_t slen;
     int32_t slot;
     int32_t lane;
     int64_t scratch;  // first column of this hit's boundary row in HitArgs::bnd (unused when qlen <= kHitsChunkRows)
+    int64_t qoff;     // the hit's query: HitArgs::query[qoff, qoff + qlen)
+    int32_t qlen;
+    int32_t row;      // the hit's row in HitArgs::out
 };
 // Byte of residue j of a subject, from the start of its long slot or of its
 // block: the inter layout's groups of [64 lanes][16 codes], or plain bytes.
@@ -409,9 +415,9 @@ __host__ __device__ constexpr uint64_t hit_residue_at(int lane, uint64_t j) {
     return lane < 0 ? j : (j / kGroupCols) * kGroupBytes + static_cast<uint64_t>(lane) * kGroupCols + j % kGroupCols;
 }
 struct HitArgs {
-    const uint8_t* query;      // qlen residue codes
-    int32_t qlen;
-    const int8_t* mat;         // 25 x 25, code order
+    const uint8_t* query;      // the queries' residue codes, concatenated (HitDesc::qoff, qlen)
+    int32_t qlen_max;          // the longest query of the launch (launch_hits: scratch is needed past a chunk)
+    const int8_t* mat;        // 25 x 25, code order
     int32_t gap_open;
     int32_t gap_extend;
     const uint8_t* res;        // the database's inter part and its block offsets
@@ -420,8 +426,8 @@ struct HitArgs {
     const uint64_t* loff;
     const HitDesc* hits;
     int32_t n;
-    int32_t* bnd;              // boundary rows, kHitsBndWords int32 per column (null when qlen <= kHitsChunkRows)
-    sw_hit* out;               // n rows
+    int32_t* bnd;              // boundary rows, kHitsBndWords int32 per column (null when qlen_max <= kHitsChunkRows)
+    sw_hit* out;               // the rows, indexed by HitDesc::row
 };
 hipError_t launch_hits(const HitArgs& a, hipStream_t s);
 

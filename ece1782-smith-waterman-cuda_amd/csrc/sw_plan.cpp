@@ -617,10 +617,15 @@ int64_t hits_scratch_bytes(int32_t qlen, int64_t slen) {
 }
 
 std::vector<int64_t> hits_groups(int32_t qlen, const int64_t* slens, int64_t n, int64_t budget) {
+    const std::vector<int32_t> qlens(static_cast<size_t>(std::max<int64_t>(n, 0)), qlen);
+    return hits_groups(qlens.data(), slens, n, budget);
+}
+
+std::vector<int64_t> hits_groups(const int32_t* qlens, const int64_t* slens, int64_t n, int64_t budget) {
     std::vector<int64_t> ends;
     int64_t bytes = 0, k0 = 0;
     for (int64_t k = 0; k < n; ++k) {
-        const int64_t b = hits_scratch_bytes(qlen, slens[k]);
+        const int64_t b = hits_scratch_bytes(qlens[k], slens[k]);
         if (k > k0 && bytes + b > budget) {
             ends.push_back(k);
             k0 = k;
@@ -630,6 +635,28 @@ std::vector<int64_t> hits_groups(int32_t qlen, const int64_t* slens, int64_t n, 
     }
     if (n > 0) ends.push_back(n);
     return ends;
+}
+
+int64_t hits_cost(int32_t qlen, int64_t slen) {
+    if (qlen <= 0 || slen <= 0) return 0;
+    constexpr int64_t kWaveRows = swk::kLanes * swk::kHitsRowsPerLane;
+    const int64_t nblk = (slen + swk::kLanes - 1 + swk::kLanes - 1) / swk::kLanes;  // blocks of the slen + 63 steps
+    int64_t rounds = 0;
+    for (int64_t c0 = 0; c0 < qlen; c0 += swk::kHitsChunkRows) {
+        const int64_t rows = std::min<int64_t>(qlen - c0, swk::kHitsChunkRows);
+        rounds += nblk + 2 * ((rows + kWaveRows - 1) / kWaveRows - 1);
+    }
+    return rounds;
+}
+
+std::vector<int64_t> hits_order(const int32_t* qlens, const int64_t* slens, int64_t n) {
+    std::vector<int64_t> order(static_cast<size_t>(std::max<int64_t>(n, 0))), cost(order.size());
+    for (size_t k = 0; k < order.size(); ++k) {
+        order[k] = static_cast<int64_t>(k);
+        cost[k] = hits_cost(qlens[k], slens[k]);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return cost[a] > cost[b]; });
+    return order;
 }
 
 }  // namespace swplan

@@ -178,5 +178,18 @@ constexpr int64_t kHitsScratchBudget = int64_t(1) << 30;
 // hits whose scratch fits the budget; a single hit over the budget forms its
 // own group.  ends.back() == n; empty for n == 0.
 std::vector<int64_t> hits_groups(int32_t qlen, const int64_t* slens, int64_t n, int64_t budget = kHitsScratchBudget);
+// ... of hits with a query each (sw_hit_stats_batch: a launch mixes queries);
+// a hit whose query fits one chunk adds 0 bytes.  Scratch belongs to the hit,
+// never to the subject: two queries on one subject get a boundary row each.
+std::vector<int64_t> hits_groups(const int32_t* qlens, const int64_t* slens, int64_t n,
+                                 int64_t budget = kHitsScratchBudget);
+// A hit's serial length in the kernel's own rounds (sw_hits.hip: a round is
+// 64 steps of every wave between two barriers): per chunk, the blocks of its
+// slen + 63 steps plus two rounds for each further wave that holds a query
+// row.  0 for an empty query or subject (the workgroup returns at once).
+int64_t hits_cost(int32_t qlen, int64_t slen);
+// The order hits launch in: cost descending, equal costs in the caller's
+// order, so the longest wavefronts start in the first wave of workgroups.
+std::vector<int64_t> hits_order(const int32_t* qlens, const int64_t* slens, int64_t n);
 
 }  // namespace swplan

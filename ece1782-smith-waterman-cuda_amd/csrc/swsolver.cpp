@@ -580,6 +580,103 @@ std::vector<sw_hit> smith_waterman_cuda_hits(FASTAQuery& query, FASTADatabase& d
     return out;
 }
 
+bool sw_solver_read_queries(const std::string& path, std::vector<std::string>* names, std::vector<std::string>* seqs,
+                            std::string* err) {
+    auto bad = [&](const std::string& why) {
+        if (err) *err = path + ": " + why;
+        return false;
+    };
+    std::ifstream in(path.c_str());
+    if (!in) return bad("cannot open query file");
+    std::vector<std::string> nm, sq;
+    std::string line;
+    while (std::getline(in, line)) {
+        if (!line.empty() && line[0] == '>') {
+            const size_t a = line.find_first_not_of(" \t", 1);
+            const size_t b = a == std::string::npos ? a : line.find_first_of(" \t\r", a);
+            nm.push_back(a == std::string::npos ? std::string() : line.substr(a, b == std::string::npos ? b : b - a));
+            sq.emplace_back();
+            continue;
+        }
+        for (char c : line) {
+            if (std::isspace(static_cast<unsigned char>(c))) continue;
+            if (sq.empty()) return bad("residues before the first '>' line");
+            sq.back() += c;
+        }
+    }
+    if (sq.empty()) return bad("no '>' line: not a FASTA file");
+    if (names) names->swap(nm);
+    if (seqs) seqs->swap(sq);
+    return true;
+}
+
+namespace {
+// The shared front of the two batch calls: k, the database as written with
+// its record ids, the queries as written, concatenated; then `run` under the
+// set scoring.
+template <class Run>
+void batch_call(const std::vector<std::string>& seqs, FASTADatabase& db, int k, const char* what, Run run) {
+    if (k < 1 || k > 4096) throw std::invalid_argument("a batch of queries needs 1 <= k <= 4096");
+    std::lock_guard<std::mutex> lock(g_mu);
+    const Flat f = timed_flatten(db, true);
+    const int64_t n = static_cast<int64_t>(f.record_ids.size());
+    for (int id : f.record_ids)
+        if (id < 0) throw std::invalid_argument("a batch of queries needs record ids (a FASTA header per subject)");
+    std::vector<int64_t> qoffs(seqs.size() + 1, 0);
+    for (size_t q = 0; q < seqs.size(); ++q) qoffs[q + 1] = qoffs[q] + static_cast<int64_t>(seqs[q].size());
+    std::vector<uint8_t> qc(static_cast<size_t>(qoffs.back()));
+    for (size_t q = 0; q < seqs.size(); ++q)
+        check(sw_encode(seqs[q].data(), static_cast<int64_t>(seqs[q].size()), qc.data() + qoffs[q]), "sw_encode");
+    const sw_scoring sc = {g_sc.has_matrix ? g_sc.mat : nullptr, g_sc.go, g_sc.ge};
+    std::vector<int32_t> ids(f.record_ids.begin(), f.record_ids.end());
+    g_timing.gpus = 1;
+    double t0 = now_s();
+    sw_handle* h = handle();
+    g_timing.init_s = now_s() - t0;
+    t0 = now_s();
+    sw_db* sdb = nullptr;
+    check(sw_db_create(h, f.residues.data(), f.offsets.data(), n, ids.data(), &sdb), "sw_db_create");
+    g_timing.upload_s = now_s() - t0;
+    t0 = now_s();
+    const int rc = run(h, sdb, qc.data(), qoffs.data(), static_cast<int32_t>(seqs.size()), &sc);
+    g_timing.scan_s = now_s() - t0;
+    sw_db_free(sdb);
+    check(rc, what);
+}
+}  // namespace
+
+std::vector<std::vector<seqid_score>> smith_waterman_cuda_batch_topk(const std::vector<std::string>& seqs,
+                                                                     FASTADatabase& db, int k) {
+    std::vector<int64_t> keys(seqs.size() * static_cast<size_t>(std::max(k, 0)));
+    batch_call(seqs, db, k, "sw_scan_batch_topk",
+               [&](sw_handle* h, sw_db* sdb, const uint8_t* qc, const int64_t* qoffs, int32_t nq, const sw_scoring* sc) {
+                   return sw_scan_batch_topk(h, sdb, qc, qoffs, nq, sc, k, keys.data());
+               });
+    std::vector<std::vector<seqid_score>> out(seqs.size());
+    for (size_t q = 0; q < seqs.size(); ++q)
+        for (int i = 0; i < k; ++i) {
+            const int64_t key = keys[q * static_cast<size_t>(k) + i];
+            if (key == INT64_MIN) break;  // fewer subjects than k
+            out[q].push_back(std::make_pair(static_cast<int>((int64_t{1} << 31) - 1 - (key & 0xffffffff)),
+                                            static_cast<int>(key >> 32)));
+        }
+    return out;
+}
+
+std::vector<std::vector<sw_hit>> smith_waterman_cuda_batch_hits(const std::vector<std::string>& seqs,
+                                                                FASTADatabase& db, int k) {
+    std::vector<sw_hit> rows(seqs.size() * static_cast<size_t>(std::max(k, 0)));
+    int32_t nhits = 0;
+    batch_call(seqs, db, k, "sw_scan_batch_hits",
+               [&](sw_handle* h, sw_db* sdb, const uint8_t* qc, const int64_t* qoffs, int32_t nq, const sw_scoring* sc) {
+                   return sw_scan_batch_hits(h, sdb, qc, qoffs, nq, sc, k, rows.data(), &nhits);
+               });
+    std::vector<std::vector<sw_hit>> out(seqs.size());
+    for (size_t q = 0; q < seqs.size(); ++q)
+        out[q].assign(rows.begin() + static_cast<int64_t>(q) * k, rows.begin() + static_cast<int64_t>(q) * k + nhits);
+    return out;
+}
+
 void smith_waterman_cuda(FASTAQuery& query, FASTADatabase& db, std::vector<seqid_score>& result) {
     std::lock_guard<std::mutex> lock(g_mu);  // the reference is not re-entrant either
     const Flat f = timed_flatten(db, g_sc.custom);

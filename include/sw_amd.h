@@ -414,8 +414,28 @@ SW_API int sw_align(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t
  * (under linear gaps every gap residue is a DP opening; the count does not
  * depend on that).  qlen + subject length < 2^31.  Arguments, error codes
  * and faults as sw_align.
- * Out of scope: the PSSM forms, sw_group_*, batches of queries, E-values and
- * bit scores, and the ops string (that is sw_align's job).               */
+ * Batches of queries (0.4.0; queries as in sw_scan_batch: concatenated codes
+ * and nq+1 offsets), all synchronous, 1 <= k <= 4096, 0 <= n < 2^31:
+ *   sw_scan_batch_topk : every query's device ranking, keys_host[nq][k] in
+ *                  sw_topk_device's key form.  The scans run back to back,
+ *                  each followed by its ranking, behind one score row: one
+ *                  copy and one synchronisation per call, device memory
+ *                  O(max_id + nq k).  An empty query ranks all-zero scores
+ *                  (ids ascending); an empty database gives INT64_MIN keys;
+ *                  nq == 0 writes nothing.
+ *   sw_hit_stats_batch : the rows of the n pairs (query qidx[i], result id
+ *                  ids[i]) into out[i], in the caller's order.  One launch
+ *                  sequence mixes the queries, longest alignment first, and
+ *                  every hit has its own scratch (two queries may hit one
+ *                  subject).  A qidx outside [0, nq) or an id the database
+ *                  does not hold is SW_E_INVALID.
+ *   sw_scan_batch_hits : sw_scan_batch_topk, then the rows of every query's
+ *                  ids in key order: out[nq][k] (stride k; rows past *nhits
+ *                  are not written), *nhits = min(k, subjects), the same
+ *                  for every query.  Two host synchronisations per call,
+ *                  whatever nq is.
+ * Out of scope: the PSSM forms, sw_group_*, E-values and bit scores, and
+ * the ops string (that is sw_align's job).                                */
 typedef struct sw_hit {
     int32_t id, score;
     int32_t q_begin, q_end, s_begin, s_end;   /* 1-based, inclusive, as sw_alignment */
@@ -430,6 +450,15 @@ SW_API int sw_hit_stats(sw_handle* h, const sw_db* db, const uint8_t* query, int
                         const sw_scoring* sc, const int32_t* ids, int32_t n, sw_hit* out);
 SW_API int sw_scan_hits(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen,
                         const sw_scoring* sc, int32_t k, sw_hit* out, int32_t* nhits);
+SW_API int sw_scan_batch_topk(sw_handle* h, const sw_db* db, const uint8_t* queries,
+                              const int64_t* qoffsets, int32_t nq, const sw_scoring* sc,
+                              int32_t k, int64_t* keys_host);
+SW_API int sw_hit_stats_batch(sw_handle* h, const sw_db* db, const uint8_t* queries,
+                              const int64_t* qoffsets, int32_t nq, const sw_scoring* sc,
+                              const int32_t* qidx, const int32_t* ids, int64_t n, sw_hit* out);
+SW_API int sw_scan_batch_hits(sw_handle* h, const sw_db* db, const uint8_t* queries,
+                              const int64_t* qoffsets, int32_t nq, const sw_scoring* sc,
+                              int32_t k, sw_hit* out, int32_t* nhits);
 
 /* ---- profile (PSSM) queries ------------------------------------------------
  * A position-specific scoring matrix in the place of a query: a [qlen][25]

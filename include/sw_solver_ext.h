@@ -78,6 +78,26 @@ std::vector<seqid_score> smith_waterman_cuda_topk(FASTAQuery& query, FASTADataba
  * a record id. */
 std::vector<sw_hit> smith_waterman_cuda_hits(FASTAQuery& query, FASTADatabase& db, int k);
 
+/* Batches of queries (sw_amd.h sw_scan_batch_topk / sw_scan_batch_hits;
+ * `main --queries FILE`).  sw_solver_read_queries reads a multi-record FASTA
+ * file: each line starting with '>' opens a record, named by the header's
+ * first word (empty when there is none); the lines up to the next '>' are its
+ * residues, white space and blank lines dropped; a record may hold none.
+ * False and *err when the file cannot be opened, holds no '>' line, or has
+ * residues before the first one.
+ * smith_waterman_cuda_batch_topk / _batch_hits return, per query in the
+ * order given, what smith_waterman_cuda_topk / _hits return for it, from one
+ * call of the library: the queries as written (no '/' padding, as
+ * smith_waterman_cuda_hits), the subjects as written, under the scoring of
+ * sw_solver_set_scoring.  1 <= k <= 4096; one GPU; std::invalid_argument for
+ * another k or a subject without a record id. */
+bool sw_solver_read_queries(const std::string& path, std::vector<std::string>* names, std::vector<std::string>* seqs,
+                            std::string* err);
+std::vector<std::vector<seqid_score> > smith_waterman_cuda_batch_topk(const std::vector<std::string>& seqs,
+                                                                      FASTADatabase& db, int k);
+std::vector<std::vector<sw_hit> > smith_waterman_cuda_batch_hits(const std::vector<std::string>& seqs,
+                                                                 FASTADatabase& db, int k);
+
 /* Profile (PSSM) queries (sw_amd.h sw_pssm_*; `main --pssm FILE`).
  * sw_solver_read_pssm reads a text PSSM into rows ([positions][25] int8 in
  * code order) and its consensus (one letter per position):
