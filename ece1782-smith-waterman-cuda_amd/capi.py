@@ -35,6 +35,8 @@ EXPORTED = (
     "sw_scan_batch_topk", "sw_hit_stats_batch", "sw_scan_batch_hits",
     "sw_pssm_create", "sw_pssm_free", "sw_pssm_length", "sw_scan_pssm", "sw_scan_pssm_device",
     "sw_scan_pssm_topk", "sw_align_pssm",
+    "sw_score_hist_device", "sw_score_hist", "sw_calib_fit", "sw_calib_sig",
+    "sw_scan_hits_sig", "sw_scan_batch_hits_sig", "sw_scan_pssm_topk_calib",
     "sw_db_save", "sw_db_load", "sw_db_subjects", "sw_db_create_synthetic", "sw_synth_tables",
     "sw_synth_lengths", "sw_group_create", "sw_group_destroy", "sw_group_info", "sw_group_handle",
     "sw_group_db_create", "sw_group_db_free", "sw_group_db_shard", "sw_group_scan", "sw_group_topk",
@@ -74,6 +76,39 @@ class Hit(ctypes.Structure):
 
     def as_dict(self):
         return {f: getattr(self, f) for f in self.FIELDS}
+
+
+# The calibration table's shape and the status bits (include/sw_amd.h
+# SW_CALIB_*): length bins x score columns, the last column clips.
+CALIB_LBINS = 128
+CALIB_SBINS = 512
+CALIB_CLIPPED = 1
+CALIB_FEW = 2
+CALIB_DEGENERATE = 4
+
+
+class Calib(ctypes.Structure):
+    """sw_calib (include/sw_amd.h): one scan's calibration."""
+    _fields_ = [("size", ctypes.c_int32), ("status", ctypes.c_int32), ("qlen", ctypes.c_int32),
+                ("fits", ctypes.c_int32), ("n_db", ctypes.c_int64), ("n_fit", ctypes.c_int64),
+                ("n_clipped", ctypes.c_int64), ("n_skipped", ctypes.c_int64),
+                ("a", ctypes.c_double), ("c", ctypes.c_double), ("sigma", ctypes.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+    def copy(self):
+        c = Calib()
+        ctypes.memmove(ctypes.byref(c), ctypes.byref(self), ctypes.sizeof(Calib))
+        return c
+
+
+class Sig(ctypes.Structure):
+    """sw_sig (include/sw_amd.h): a hit's E-value, bit score and z-score."""
+    _fields_ = [("evalue", ctypes.c_double), ("bits", ctypes.c_double), ("z", ctypes.c_double)]
+
+    def as_dict(self):
+        return {"evalue": self.evalue, "bits": self.bits, "z": self.z}
 
 
 # The hit-table kernel's shape (csrc/sw_kernels.h kHitsRowsPerLane, kHitsWaves,
@@ -186,6 +221,16 @@ def lib():
                                               ctypes.POINTER(Hit)]),
         "sw_scan_batch_hits": (ctypes.c_int, [vp, vp, u8p, i64p, i32, ctypes.POINTER(Scoring), i32,
                                               ctypes.POINTER(Hit), i32p]),
+        "sw_score_hist_device": (ctypes.c_int, [vp, vp, vp, vp]),
+        "sw_score_hist": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(ctypes.c_uint32)]),
+        "sw_calib_fit": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32), i32, ctypes.POINTER(Calib)]),
+        "sw_calib_sig": (ctypes.c_int, [ctypes.POINTER(Calib), i32, i32, ctypes.POINTER(Sig)]),
+        "sw_scan_hits_sig": (ctypes.c_int, [vp, vp, u8p, i32, ctypes.POINTER(Scoring), i32, ctypes.POINTER(Hit),
+                                            ctypes.POINTER(Sig), i32p, ctypes.POINTER(Calib)]),
+        "sw_scan_batch_hits_sig": (ctypes.c_int, [vp, vp, u8p, i64p, i32, ctypes.POINTER(Scoring), i32,
+                                                  ctypes.POINTER(Hit), ctypes.POINTER(Sig), i32p,
+                                                  ctypes.POINTER(Calib)]),
+        "sw_scan_pssm_topk_calib": (ctypes.c_int, [vp, vp, vp, i32, i32, i32, i64p, ctypes.POINTER(Calib)]),
         "sw_pssm_create": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int8), i32, ctypes.POINTER(vp)]),
         "sw_pssm_free": (ctypes.c_int, [vp]),
         "sw_pssm_length": (ctypes.c_int, [vp, i32p]),
@@ -619,6 +664,46 @@ class Database:
         _check(lib().sw_scan_hits(self.handle.ptr, self._d, qp, len(q), sc.ptr(), k, out, ctypes.byref(nhits)))
         return [out[i].as_dict() for i in range(nhits.value)]
 
+    def score_hist(self, scores_dev_ptr, hist_dev_ptr=None):
+        """The calibration table of a device score array (n_out int32, as a
+        scan wrote it): uint32 [CALIB_LBINS, CALIB_SBINS], one count per
+        subject at [length bin, clamped score] (sw_score_hist).  With
+        hist_dev_ptr: asynchronous into that device buffer (256 KB;
+        sw_score_hist_device), returns None."""
+        if hist_dev_ptr is not None:
+            _check(lib().sw_score_hist_device(self.handle.ptr, self._d, ctypes.c_void_p(scores_dev_ptr),
+                                              ctypes.c_void_p(hist_dev_ptr)))
+            return None
+        out = np.zeros((CALIB_LBINS, CALIB_SBINS), dtype=np.uint32)
+        _check(lib().sw_score_hist(self.handle.ptr, self._d, ctypes.c_void_p(scores_dev_ptr),
+                                   out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+        return out
+
+    def scan_hits_sig(self, query_codes, k, matrix=None, gap=2, gap_extend=None):
+        """scan_hits with every row's E-value, bit score and z-score (keys
+        evalue, bits, z beside sw_hit's) from the scan's own calibration
+        (sw_scan_hits_sig).  Returns (rows, Calib)."""
+        q, qp = _u8(query_codes)
+        sc = _ScoringArg(matrix, gap, gap if gap_extend is None else gap_extend)
+        out = (Hit * max(int(k), 1))()
+        sig = (Sig * max(int(k), 1))()
+        cal = Calib()
+        nhits = ctypes.c_int32(0)
+        _check(lib().sw_scan_hits_sig(self.handle.ptr, self._d, qp, len(q), sc.ptr(), k, out, sig,
+                                      ctypes.byref(nhits), ctypes.byref(cal)))
+        return [dict(out[i].as_dict(), **sig[i].as_dict()) for i in range(nhits.value)], cal
+
+    def scan_pssm_topk_calib(self, pssm, k, gap_open=2, gap_extend=None):
+        """scan_pssm_topk and the scan's calibration (sw_scan_pssm_topk_calib):
+        (keys, Calib); calib_sig with the keys' scores and subjects() lengths
+        gives the hits' significance."""
+        out = np.zeros(k, dtype=np.int64)
+        cal = Calib()
+        _check(lib().sw_scan_pssm_topk_calib(self.handle.ptr, self._d, pssm.ptr, gap_open,
+                                             gap_open if gap_extend is None else gap_extend, k,
+                                             out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(cal)))
+        return out, cal
+
     def scan_pssm(self, pssm, gap_open=2, gap_extend=None):
         """Synchronous scan of a Pssm; int32 scores indexed by id (sw_scan_pssm)."""
         out = np.zeros(self.n_out, dtype=np.int32)
@@ -730,6 +815,44 @@ class Database:
                                         offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nq, sc.ptr(), k, out,
                                         ctypes.byref(nhits)))
         return [[out[q * kk + i].as_dict() for i in range(nhits.value)] for q in range(nq)]
+
+    def scan_batch_hits_sig(self, queries, k, matrix=None, gap=2, gap_extend=None):
+        """scan_hits_sig for every query of a batch in one call
+        (sw_scan_batch_hits_sig: still two host synchronisations).  Returns
+        (rows, calibs): len(queries) lists of row dicts and as many Calibs."""
+        cat, offs = self._cat(queries)
+        c, cp = _u8(cat)
+        sc = _ScoringArg(matrix, gap, gap if gap_extend is None else gap_extend)
+        nq, kk = len(queries), max(int(k), 1)
+        out = (Hit * max(nq * kk, 1))()
+        sig = (Sig * max(nq * kk, 1))()
+        cal = (Calib * max(nq, 1))()
+        nhits = ctypes.c_int32(0)
+        _check(lib().sw_scan_batch_hits_sig(self.handle.ptr, self._d, cp,
+                                            offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nq, sc.ptr(), k, out,
+                                            sig, ctypes.byref(nhits), cal))
+        rows = [[dict(out[q * kk + i].as_dict(), **sig[q * kk + i].as_dict()) for i in range(nhits.value)]
+                for q in range(nq)]
+        return rows, [cal[q].copy() for q in range(nq)]
+
+
+def calib_fit(hist, qlen):
+    """The calibration of a [CALIB_LBINS, CALIB_SBINS] count table
+    (sw_calib_fit; host only): a Calib."""
+    t = np.ascontiguousarray(hist, dtype=np.uint32)
+    if t.size != CALIB_LBINS * CALIB_SBINS:
+        raise SWError("a calibration table is [%d, %d] uint32" % (CALIB_LBINS, CALIB_SBINS))
+    cal = Calib()
+    _check(lib().sw_calib_fit(t.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), int(qlen), ctypes.byref(cal)))
+    return cal
+
+
+def calib_sig(calib, score, slen):
+    """(evalue, bits, z) of a hit of this score against a subject of this
+    length under a Calib (sw_calib_sig; host only)."""
+    s = Sig()
+    _check(lib().sw_calib_sig(ctypes.byref(calib), int(score), int(slen), ctypes.byref(s)))
+    return s.evalue, s.bits, s.z
 
 
 class Group:

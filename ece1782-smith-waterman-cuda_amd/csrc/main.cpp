@@ -31,6 +31,14 @@
 //   id score q_begin q_end s_begin s_end s_len length identities positives gap_opens gaps
 // under the scoring flags, on one GPU; it cannot be combined with --pssm,
 // --topk or --gpus N > 1, and is checked before any file is read.
+// E-values and bit scores: --evalue, valid only with --hits (with or without
+// --queries; checked before any file is read), appends two columns to every
+// row, evalue (%.3g) and bits (%.1f), from the scan's own calibration
+// (sw_scan_hits_sig, sw_amd.h), and prints one line per query before its rows:
+//   # calibration a c sigma n_fit n_clipped status
+// A calibration that clipped or is degenerate also warns on stderr: the
+// scoring has no local-alignment statistic, or the database is too uniform,
+// and the two columns mean nothing.  Without --evalue the output is unchanged.
 // Batches of queries: --queries FILE takes the place of --query: a FASTA file
 // of several records (sw_solver_read_queries), searched in one call of the
 // library (sw_scan_batch_hits / sw_scan_batch_topk) against a FASTA or a
@@ -44,6 +52,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -79,7 +88,9 @@ void usage() {
               << "  --gap-extend arg      Cost of each further gap residue (default: --gap-open, linear)\n"
               << "  --topk arg            Print only the arg best subjects (score desc, id asc)\n"
               << "  --hits arg            Print the arg best subjects (1..4096) as a hit table: id score q_begin\n"
-              << "                        q_end s_begin s_end s_len length identities positives gap_opens gaps\n";
+              << "                        q_end s_begin s_end s_len length identities positives gap_opens gaps\n"
+              << "  --evalue              With --hits: append evalue and bits to each row (calibrated on the\n"
+              << "                        scan's own scores) and print a '# calibration' line per query\n";
 }
 
 // a whole-string integer in [lo, hi]
@@ -107,17 +118,22 @@ int main(int argc, char* argv[]) {
         if (eq != std::string::npos) {
             val = key.substr(eq + 1);
             key = key.substr(0, eq);
-        } else if (key != "metrics-json") {
+        } else if (key != "metrics-json" && key != "evalue") {
             if (i + 1 >= argc) { usage(); return 1; }
             val = argv[++i];
         }
         if (key != "query" && key != "db" && key != "metrics-json" && key != "make-db" && key != "gpus" &&
             key != "matrix" && key != "gap-open" && key != "gap-extend" && key != "topk" && key != "pssm" && key != "hits" &&
-            key != "queries") {
+            key != "queries" && key != "evalue") {
             std::cerr << "unrecognised option '--" << key << "'\n";
             return 1;
         }
         opt[key] = val;
+    }
+    const bool evalue = opt.count("evalue") != 0;
+    if (evalue && !opt.count("hits") && !help) {  // checked before any file is read
+        std::cerr << "--evalue needs --hits K: it adds columns to the hit table\n";
+        return 1;
     }
     const bool use_queries = opt.count("queries") != 0;
     if (use_queries && !help) {  // checked before any file is read
@@ -248,6 +264,9 @@ int main(int argc, char* argv[]) {
     std::vector<sw_hit> rows;  // --hits
     std::vector<std::vector<seqid_score> > bresult;  // --queries: one block per query
     std::vector<std::vector<sw_hit> > brows;
+    std::vector<sw_sig> sigs;  // --evalue: beside rows / brows
+    std::vector<std::vector<sw_sig> > bsigs;
+    std::vector<sw_calib> calibs;  // ... one per query
     int64_t num_subjects = 0, length_sum = 0;
     double solve_s = 0, parse_s = 0;
     if (!binary) {
@@ -256,7 +275,12 @@ int main(int argc, char* argv[]) {
         parse_s = now_s() - t_parse;
         const double t_solve = now_s();
         try {
-            if (use_queries && hits) brows = smith_waterman_cuda_batch_hits(qseqs, db, hits);
+            if (use_queries && hits && evalue) brows = smith_waterman_cuda_batch_hits_sig(qseqs, db, hits, &bsigs, &calibs);
+            else if (hits && evalue) {
+                calibs.resize(1);
+                rows = smith_waterman_cuda_hits_sig(query, db, hits, &sigs, &calibs[0]);
+            }
+            else if (use_queries && hits) brows = smith_waterman_cuda_batch_hits(qseqs, db, hits);
             else if (use_queries) bresult = smith_waterman_cuda_batch_topk(qseqs, db, topk);
             else if (hits) rows = smith_waterman_cuda_hits(query, db, hits);
             else if (use_pssm) result = smith_waterman_cuda_pssm(prows, db, topk);
@@ -309,11 +333,19 @@ int main(int argc, char* argv[]) {
             if (hits) {
                 std::vector<sw_hit> all(qseqs.size() * static_cast<size_t>(hits));
                 int32_t nhits = 0;
-                if (sw_scan_batch_hits(h, sdb, cat.data(), qoffs.data(), nq, &sc, hits, all.data(), &nhits))
+                std::vector<sw_sig> allsig(evalue ? all.size() : 0);
+                calibs.resize(evalue ? qseqs.size() : 0);
+                if (evalue ? sw_scan_batch_hits_sig(h, sdb, cat.data(), qoffs.data(), nq, &sc, hits, all.data(),
+                                                    allsig.data(), &nhits, calibs.data())
+                           : sw_scan_batch_hits(h, sdb, cat.data(), qoffs.data(), nq, &sc, hits, all.data(), &nhits))
                     return die("sw_scan_batch_hits");
-                for (size_t i = 0; i < qseqs.size(); ++i)
+                for (size_t i = 0; i < qseqs.size(); ++i) {
                     brows.push_back(std::vector<sw_hit>(all.begin() + static_cast<int64_t>(i) * hits,
                                                         all.begin() + static_cast<int64_t>(i) * hits + nhits));
+                    if (evalue)
+                        bsigs.push_back(std::vector<sw_sig>(allsig.begin() + static_cast<int64_t>(i) * hits,
+                                                            allsig.begin() + static_cast<int64_t>(i) * hits + nhits));
+                }
             } else {
                 std::vector<int64_t> keys(qseqs.size() * static_cast<size_t>(topk));
                 if (sw_scan_batch_topk(h, sdb, cat.data(), qoffs.data(), nq, &sc, topk, keys.data()))
@@ -330,9 +362,14 @@ int main(int argc, char* argv[]) {
         } else if (hits) {
             rows.resize(static_cast<size_t>(hits));
             int32_t nhits = 0;
-            if (sw_scan_hits(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, hits, rows.data(), &nhits))
+            sigs.resize(evalue ? rows.size() : 0);
+            calibs.resize(evalue ? 1 : 0);
+            if (evalue ? sw_scan_hits_sig(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, hits, rows.data(),
+                                          sigs.data(), &nhits, calibs.data())
+                       : sw_scan_hits(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, hits, rows.data(), &nhits))
                 return die("sw_scan_hits");
             rows.resize(static_cast<size_t>(nhits));
+            sigs.resize(evalue ? rows.size() : 0);
         } else if (topk && topk <= 4096) {
             std::vector<int64_t> keys(static_cast<size_t>(topk));
             if (use_pssm ? sw_scan_pssm_topk(h, sdb, pssm, gap_open, gap_extend, topk, keys.data())
@@ -381,18 +418,44 @@ int main(int argc, char* argv[]) {
         for (vector<seqid_score>::const_iterator it = v.begin(); it != v.end(); ++it)
             cout << (*it).first << ":" << (*it).second << "\n";
     };
-    auto print_rows = [](const std::vector<sw_hit>& v) {
-        for (const sw_hit& r : v)
+    // sig (nullable): the rows' significances, two more columns
+    auto print_rows = [](const std::vector<sw_hit>& v, const std::vector<sw_sig>* sig) {
+        for (size_t i = 0; i < v.size(); ++i) {
+            const sw_hit& r = v[i];
             cout << r.id << "\t" << r.score << "\t" << r.q_begin << "\t" << r.q_end << "\t" << r.s_begin << "\t"
                  << r.s_end << "\t" << r.s_len << "\t" << r.length << "\t" << r.identities << "\t" << r.positives
-                 << "\t" << r.gap_opens << "\t" << r.gaps << "\n";
+                 << "\t" << r.gap_opens << "\t" << r.gaps;
+            if (sig) {
+                char buf[64];
+                std::snprintf(buf, sizeof buf, "\t%.3g\t%.1f", (*sig)[i].evalue, (*sig)[i].bits);
+                cout << buf;
+            }
+            cout << "\n";
+        }
+    };
+    // --evalue: a query's calibration line, and the warning when it carries no statistic
+    auto print_calib = [](const sw_calib& c, size_t query_index) {
+        char buf[192];
+        std::snprintf(buf, sizeof buf, "# calibration %.6g %.6g %.6g %lld %lld %d\n", c.a, c.c, c.sigma,
+                      static_cast<long long>(c.n_fit), static_cast<long long>(c.n_clipped), c.status);
+        cout << buf;
+        if (c.status & SW_CALIB_CLIPPED)
+            std::cerr << "warning: query " << query_index << ": " << c.n_clipped << " of " << c.n_db
+                      << " scores reach the calibration's clip column (511): under this scoring scores grow with"
+                         " length and the evalue and bits columns mean nothing\n";
+        if (c.status & SW_CALIB_DEGENERATE)
+            std::cerr << "warning: query " << query_index
+                      << ": the calibration is degenerate (too few or too uniform scores): every evalue is the"
+                         " database's size\n";
     };
     print_scores(result);
-    print_rows(rows);
+    if (evalue && !use_queries && !calibs.empty()) print_calib(calibs[0], 0);
+    print_rows(rows, evalue && !use_queries ? &sigs : nullptr);
     // --queries: a block per query, in file order (index from 0; "-" for a header without a name)
     for (size_t i = 0; i < qseqs.size(); ++i) {
         cout << "# query " << i << " " << (qnames[i].empty() ? "-" : qnames[i]) << " " << qseqs[i].size() << "\n";
-        if (i < brows.size()) print_rows(brows[i]);
+        if (evalue && i < calibs.size()) print_calib(calibs[i], i);
+        if (i < brows.size()) print_rows(brows[i], evalue && i < bsigs.size() ? &bsigs[i] : nullptr);
         if (i < bresult.size()) print_scores(bresult[i]);
     }
 

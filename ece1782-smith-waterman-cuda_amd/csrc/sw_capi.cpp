@@ -28,6 +28,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "sw_calib.h"
 #include "sw_dbfile.h"
 #include "sw_host.h"
 #include "sw_pack.h"
@@ -252,6 +253,12 @@ struct sw_handle {
     DevPtr<int32_t> d_scores;  // for the synchronous sw_scan
     size_t scores_cap = 0;
     DevPtr<int64_t> d_topk_work;  // device top-K workspace
+    DevPtr<uint32_t> d_hist;      // the calibration table of the synchronous sw_score_hist
+    // pinned landing area of the scans' calibration tables (the _sig and _calib
+    // forms): a copy into pageable memory would make the host wait inside
+    // hipMemcpyAsync, one more synchronisation in all but name
+    HostPtr<uint32_t> h_hist;
+    size_t hist_cap = 0;  // ... in tables
     std::string last_kernel = "none";  // per-wave inter kernel of the last scan
     std::string last_intra = "none";   // long-subject kernel of the last scan
     size_t topk_cap = 0;
@@ -383,6 +390,7 @@ struct sw_db {
         DevPtr<uint32_t> d_blk_cols;  // block widths rounded to 8 columns (sw_inter_x2s)
         DevPtr<int32_t> d_lane_ids;
         DevPtr<int32_t> d_ids;        // every subject's result id (sw_scan_topk), on first use
+        DevPtr<int32_t> d_slen;       // every subject's length, in the same order (sw_score_hist), on first use
         DevPtr<int32_t> d_bnd_h, d_bnd_f;
         // two rescue lists [count, block ids...] of nblocks + 1 ints each: the
         // 16-bit kernels' flagged blocks (list A), and the fp16 chain's second
@@ -1006,18 +1014,14 @@ struct RankReq {
     int64_t* out;
 };
 
-// The ranking input over a database's subjects: its scores through the
-// result ids (db->lay.d_ids.get(), uploaded on first use), or directly when the ids
-// are 0 .. n-1 in order (the default).
-int rank_src(sw_db* db, const int32_t* scores, const RankReq& rq, swk::TopkSrc* src) {
+// A database's result ids on the device (db->lay.d_ids, uploaded on first
+// use), or null when the ids are 0 .. n-1 in order (the default).
+int subject_ids(sw_db* db, const int32_t** rid) {
     if (db->rid_identity < 0) {
         db->rid_identity = db->max_id + 1 == db->n;
         for (int64_t k = 0; db->rid_identity == 1 && k < db->n; ++k) db->rid_identity = db->h_ids[k] == k;
     }
-    *src = swk::TopkSrc{};
-    src->scores = scores;
-    src->gid = rq.gid;
-    src->id_base = rq.id_base;
+    *rid = nullptr;
     if (!db->rid_identity) {
         if (!db->lay.d_ids.get()) {
             HIPCHECK(swk::dev_alloc(db->lay.d_ids, static_cast<size_t>(db->n) * sizeof(int32_t)));
@@ -1025,8 +1029,40 @@ int rank_src(sw_db* db, const int32_t* scores, const RankReq& rq, swk::TopkSrc* 
                                hipMemcpyHostToDevice));
             db->lay.device_bytes += static_cast<size_t>(db->n) * sizeof(int32_t);
         }
-        src->rid = db->lay.d_ids.get();
+        *rid = db->lay.d_ids.get();
     }
+    return SW_OK;
+}
+
+// The ranking input over a database's subjects: its scores through the
+// result ids, or directly when those are the identity.
+int rank_src(sw_db* db, const int32_t* scores, const RankReq& rq, swk::TopkSrc* src) {
+    *src = swk::TopkSrc{};
+    src->scores = scores;
+    src->gid = rq.gid;
+    src->id_base = rq.id_base;
+    return subject_ids(db, &src->rid);
+}
+
+// The calibration table of a score array over a database's subjects
+// (sw_calib.hip): the table zeroed, then one count per subject, on the
+// handle's stream.  The subjects' lengths go up on first use, in the
+// database's own order (beside d_ids: whatever the long threshold is, the
+// table is the same).
+int hist_after(sw_handle* h, sw_db* db, const int32_t* scores_dev, uint32_t* hist_dev) {
+    HIPCHECK(hipMemsetAsync(hist_dev, 0, swcalib::kCells * sizeof(uint32_t), h->stream.get()));
+    if (db->n == 0) return SW_OK;
+    const int32_t* rid = nullptr;
+    if (int rc = subject_ids(db, &rid)) return rc;
+    if (!db->lay.d_slen.get()) {
+        std::vector<int32_t> L(static_cast<size_t>(db->n));
+        for (int64_t k = 0; k < db->n; ++k) L[k] = static_cast<int32_t>(db->h_offsets[k + 1] - db->h_offsets[k]);
+        HIPCHECK(swk::dev_alloc(db->lay.d_slen, L.size() * sizeof(int32_t)));
+        HIPCHECK(hipMemcpy(db->lay.d_slen.get(), L.data(), L.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        db->lay.device_bytes += L.size() * sizeof(int32_t);
+    }
+    HIPCHECK(swk::launch_score_hist(scores_dev, rid, db->lay.d_slen.get(), db->n, hist_dev, h->stream.get()));
+    ++h->launches;
     return SW_OK;
 }
 
@@ -1113,7 +1149,7 @@ struct Scan {
 };
 
 // Empty query: every score is 0 (the reference's kernel leaves maxScore 0).
-int scan_empty(sw_handle* h, sw_db* db, int32_t* scores_dev, bool defer, const RankReq* rq) {
+int scan_empty(sw_handle* h, sw_db* db, int32_t* scores_dev, bool defer, const RankReq* rq, uint32_t* hist) {
     int rc;
     db->last_ncoop = 0;
     db->last_npair = 0;
@@ -1125,6 +1161,7 @@ int scan_empty(sw_handle* h, sw_db* db, int32_t* scores_dev, bool defer, const R
     MARK(0, h->stream.get());
     if (db->max_id >= 0) HIPCHECK(hipMemsetAsync(scores_dev, 0, static_cast<size_t>(db->max_id + 1) * 4, h->stream.get()));
     if (rq && (rc = rank_after(h, db, scores_dev, *rq))) return rc;
+    if (hist && (rc = hist_after(h, db, scores_dev, hist))) return rc;
     for (int k = 1; k < 8; ++k) MARK(k, h->stream.get());
     h->timed = true;
     return SW_OK;
@@ -1624,16 +1661,18 @@ int print_rescue_stats(const Scan& c) {
 // tail stream beside the next scan's fp16 passes (sw_handle::tail).
 // rq (nullable): rank the scan's scores too (a top-K launch after every
 // stage that writes them, before the scan's end event).
+// hist (nullable, device): the scores' calibration table too (hist_after), at
+// the same place: after every stage that writes them, before the end event.
 // src: the query source.  The two forms differ in the scoring's checks and
 // keys here and in scan_profiles; everything else is one path.
 int scan_impl_body(sw_handle* h, const sw_db* cdb, const QuerySrc& src, int32_t* scores_dev, bool defer = false,
-                   const RankReq* rq = nullptr) {
+                   const RankReq* rq = nullptr, uint32_t* hist = nullptr) {
     sw_db* db = const_cast<sw_db*>(cdb);
     const uint8_t* query = src.codes;
     const int32_t qlen = src.qlen;
     if (!h || !db || (!src.pssm && !query && qlen > 0) || qlen < 0 || !scores_dev)
         return fail(SW_E_INVALID, "null argument");
-    if (rq) defer = false;  // the ranking reads every rescued score
+    if (rq || hist) defer = false;  // the ranking and the table read every rescued score
     const int8_t* mat = nullptr;
     int go = src.go, ge = src.ge, rc;
     if (src.pssm && (rc = check_pssm(h, src.pssm, go, ge))) return rc;
@@ -1644,7 +1683,7 @@ int scan_impl_body(sw_handle* h, const sw_db* cdb, const QuerySrc& src, int32_t*
     h->launches = 0;
     h->had_intra = false;
     if ((rc = next_events(h))) return rc;
-    if (qlen == 0) return scan_empty(h, db, scores_dev, defer, rq);
+    if (qlen == 0) return scan_empty(h, db, scores_dev, defer, rq, hist);
 
     Scan c;
     c.h = h;
@@ -1707,6 +1746,7 @@ int scan_impl_body(sw_handle* h, const sw_db* cdb, const QuerySrc& src, int32_t*
     // the scan completes on the handle's stream: so do earlier deferred tails
     if (!c.deferred && (rc = join_tails(h))) return rc;
     if (rq && (rc = rank_after(h, db, scores_dev, *rq))) return rc;
+    if (hist && (rc = hist_after(h, db, scores_dev, hist))) return rc;
     MARK(3, h->stream.get());
     h->open_slot = -1;
     h->evpool[h->nscans - 1].launches = h->launches;
@@ -1719,8 +1759,8 @@ int scan_impl_body(sw_handle* h, const sw_db* cdb, const QuerySrc& src, int32_t*
 // would not wait for the kernels this one queued.  Drain the handle's streams
 // and release the slot instead.
 int scan_impl(sw_handle* h, const sw_db* db, const QuerySrc& src, int32_t* scores_dev, bool defer = false,
-              const RankReq* rq = nullptr) {
-    const int rc = scan_impl_body(h, db, src, scores_dev, defer, rq);
+              const RankReq* rq = nullptr, uint32_t* hist = nullptr) {
+    const int rc = scan_impl_body(h, db, src, scores_dev, defer, rq, hist);
     if (h && h->open_slot >= 0) {
         (void)quiesce(h);
         h->prof[h->open_slot].pending = false;
@@ -1730,8 +1770,8 @@ int scan_impl(sw_handle* h, const sw_db* db, const QuerySrc& src, int32_t* score
 }
 
 int scan_impl(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
-              int32_t* scores_dev, bool defer = false, const RankReq* rq = nullptr) {
-    return scan_impl(h, db, seq_src(query, qlen, sc), scores_dev, defer, rq);
+              int32_t* scores_dev, bool defer = false, const RankReq* rq = nullptr, uint32_t* hist = nullptr) {
+    return scan_impl(h, db, seq_src(query, qlen, sc), scores_dev, defer, rq, hist);
 }
 
 int ensure_scores(sw_handle* h, size_t n) {
@@ -1761,23 +1801,32 @@ int scan_host(sw_handle* h, const sw_db* db, const QuerySrc& src, int32_t* score
 }
 
 // sw_scan_topk / sw_scan_pssm_topk: a scan and its ranking, k keys copied back.
-int scan_topk_host(sw_handle* h, const sw_db* cdb, const QuerySrc& src, int32_t k, int64_t* keys_host) {
+// hist_host (nullable): the scan's calibration table too (sw_calib.h), built
+// behind the keys in device memory and copied back with them.
+int scan_topk_host(sw_handle* h, const sw_db* cdb, const QuerySrc& src, int32_t k, int64_t* keys_host,
+                   uint32_t* hist_host = nullptr) {
     sw_db* db = const_cast<sw_db*>(cdb);
     if (!h || !db || !keys_host || k <= 0 || k > 4096) return fail(SW_E_INVALID, "bad argument (1 <= k <= 4096)");
     if (db->n == 0) {
         for (int32_t i = 0; i < k; ++i) keys_host[i] = INT64_MIN;
+        if (hist_host) std::memset(hist_host, 0, swcalib::kCells * sizeof(uint32_t));
         return SW_OK;
     }
     int rc;
     HIPCHECK(hipSetDevice(h->device));
     const size_t slots = static_cast<size_t>(db->max_id + 1);
-    if ((rc = ensure_scores(h, slots + static_cast<size_t>(2 * k) + 2))) return rc;  // scores, then the k keys
+    // scores, then the k keys, then the table
+    if ((rc = ensure_scores(h, slots + static_cast<size_t>(2 * k) + 2 + (hist_host ? swcalib::kCells : 0)))) return rc;
     int64_t* keys_dev = reinterpret_cast<int64_t*>(h->d_scores.get() + round_up(static_cast<int64_t>(slots), 2));
+    uint32_t* hist_dev = hist_host ? reinterpret_cast<uint32_t*>(keys_dev + k) : nullptr;
     // the ranking runs over the result ids of the subjects (rank_src)
     const RankReq rq{k, nullptr, 0, keys_dev};
-    if ((rc = scan_impl(h, db, src, h->d_scores.get(), false, &rq))) return rc;
+    if ((rc = scan_impl(h, db, src, h->d_scores.get(), false, &rq, hist_dev))) return rc;
     HIPCHECK(hipMemcpyAsync(keys_host, keys_dev, static_cast<size_t>(k) * sizeof(int64_t), hipMemcpyDeviceToHost,
                             h->stream.get()));
+    if (hist_host)
+        HIPCHECK(hipMemcpyAsync(hist_host, hist_dev, swcalib::kCells * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                h->stream.get()));
     HIPCHECK(hipStreamSynchronize(h->stream.get()));
     return check_fault(h);
 }
@@ -1807,7 +1856,9 @@ int topk_impl(sw_handle* h, const int32_t* scores, const int64_t* keys, int64_t 
 // ===========================================================================
 extern "C" {
 
-int32_t sw_version(void) { return 10000 * 0 + 100 * 4 + 0; }  // 0.2: sw_pssm_*; 0.3: sw_hit_stats, sw_scan_hits; 0.4: sw_scan_batch_topk, sw_*_hits batch forms
+// 0.2: sw_pssm_*; 0.3: sw_hit_stats, sw_scan_hits; 0.4: sw_scan_batch_topk, sw_*_hits batch forms;
+// 0.5: sw_score_hist*, sw_calib_*, the _sig and _calib scan forms
+int32_t sw_version(void) { return 10000 * 0 + 100 * 5 + 0; }
 
 #ifndef SW_SOURCE_ID
 #define SW_SOURCE_ID "unknown"
@@ -2660,29 +2711,39 @@ int check_batch_args(sw_handle* h, const sw_db* db, const uint8_t* queries, cons
 // query's scores, its rescue tail included, and the next scan's writes follow
 // it in stream order), into keys[nq][k] behind ONE score row; one copy and
 // one synchronisation end the call.
+// hist_host (nullable, [nq][128][512]): every query's calibration table too,
+// behind the keys in device memory, in the same copy sequence and
+// synchronisation.
 int batch_topk_impl(sw_handle* h, const sw_db* cdb, const uint8_t* queries, const int64_t* qoffsets, int32_t nq,
-                    const sw_scoring* sc, int32_t k, int64_t* keys_host) {
+                    const sw_scoring* sc, int32_t k, int64_t* keys_host, uint32_t* hist_host = nullptr) {
     sw_db* db = const_cast<sw_db*>(cdb);
     int rc;
     if ((rc = check_batch_args(h, db, queries, qoffsets, nq))) return rc;
     if (k <= 0 || k > 4096 || (nq > 0 && !keys_host)) return fail(SW_E_INVALID, "bad argument (1 <= k <= 4096)");
     if (nq == 0) return SW_OK;
     const size_t nkeys = static_cast<size_t>(nq) * static_cast<size_t>(k);
+    const size_t ntab = hist_host ? static_cast<size_t>(nq) * swcalib::kCells : 0;
     if (db->n == 0) {
         for (size_t i = 0; i < nkeys; ++i) keys_host[i] = INT64_MIN;
+        if (hist_host) std::memset(hist_host, 0, ntab * sizeof(uint32_t));
         return SW_OK;
     }
     HIPCHECK(hipSetDevice(h->device));
     const size_t slots = static_cast<size_t>(db->max_id + 1);
-    if ((rc = ensure_scores(h, slots + 2 * nkeys + 2))) return rc;  // the score row, then the nq x k keys
+    // the score row, then the nq x k keys, then the nq tables
+    if ((rc = ensure_scores(h, slots + 2 * nkeys + 2 + ntab))) return rc;
     int64_t* keys_dev = reinterpret_cast<int64_t*>(h->d_scores.get() + round_up(static_cast<int64_t>(slots), 2));
+    uint32_t* hist_dev = hist_host ? reinterpret_cast<uint32_t*>(keys_dev + nkeys) : nullptr;
     for (int32_t q = 0; q < nq; ++q) {
         const RankReq rq{k, nullptr, 0, keys_dev + static_cast<size_t>(q) * k};
         if ((rc = scan_impl(h, db, queries + qoffsets[q], static_cast<int32_t>(qoffsets[q + 1] - qoffsets[q]), sc,
-                            h->d_scores.get(), false, &rq)))
+                            h->d_scores.get(), false, &rq,
+                            hist_dev ? hist_dev + static_cast<size_t>(q) * swcalib::kCells : nullptr)))
             return rc;
     }
     HIPCHECK(hipMemcpyAsync(keys_host, keys_dev, nkeys * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream.get()));
+    if (hist_host)
+        HIPCHECK(hipMemcpyAsync(hist_host, hist_dev, ntab * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream.get()));
     HIPCHECK(hipStreamSynchronize(h->stream.get()));
     return check_fault(h);
 }
@@ -2710,16 +2771,44 @@ int sw_hit_stats_batch(sw_handle* h, const sw_db* db, const uint8_t* queries, co
     return check_fault(h);
 }
 
-int sw_scan_batch_hits(sw_handle* h, const sw_db* db, const uint8_t* queries, const int64_t* qoffsets, int32_t nq,
-                       const sw_scoring* sc, int32_t k, sw_hit* out, int32_t* nhits) {
-    if (!h || !db || !nhits || k <= 0 || k > 4096 || (nq > 0 && !out))
+}  // extern "C"
+
+namespace {
+// A scan's calibration from its table (sw_calib.h): the fit, and the
+// zero-length subjects the table does not hold.
+// The handle's pinned landing area holds at least n tables.
+int ensure_hist_host(sw_handle* h, size_t n, uint32_t** out) {
+    if (n > h->hist_cap) {
+        HIPCHECK(hipSetDevice(h->device));
+        HIPCHECK(hipStreamSynchronize(h->stream.get()));  // (a copy of an earlier call has long landed; be sure)
+        h->hist_cap = 0;
+        HIPCHECK(swk::host_alloc(h->h_hist, n * swcalib::kCells * sizeof(uint32_t), hipHostMallocDefault));
+        h->hist_cap = n;
+    }
+    *out = h->h_hist.get();
+    return SW_OK;
+}
+
+void calib_of(const sw_db* db, const uint32_t* hist, int32_t qlen, sw_calib* out) {
+    swcalib::fit(hist, qlen, out);
+    out->n_skipped = db->n - out->n_db;
+}
+
+// sw_scan_batch_hits; with_sig: its _sig form, the tables coming down with
+// the keys, into sig ([nq][k]) and calib (nullable, [nq]).
+int batch_hits_impl(sw_handle* h, const sw_db* db, const uint8_t* queries, const int64_t* qoffsets, int32_t nq,
+                    const sw_scoring* sc, int32_t k, sw_hit* out, int32_t* nhits, bool with_sig, sw_sig* sig,
+                    sw_calib* calib) {
+    if (!h || !db || !nhits || k <= 0 || k > 4096 || (nq > 0 && (!out || (with_sig && !sig))))
         return fail(SW_E_INVALID, "bad argument (1 <= k <= 4096)");
     *nhits = 0;
     int rc;
     if ((rc = check_batch_args(h, db, queries, qoffsets, nq))) return rc;
-    // first synchronisation: every query's keys
+    // first synchronisation: every query's keys (and table)
     std::vector<int64_t> keys(static_cast<size_t>(std::max(nq, 0)) * static_cast<size_t>(k));
-    if ((rc = batch_topk_impl(h, db, queries, qoffsets, nq, sc, k, keys.data()))) return rc;
+    uint32_t* hist = nullptr;  // (pinned: the tables come down in the keys' synchronisation)
+    if (with_sig && nq > 0 && (rc = ensure_hist_host(h, static_cast<size_t>(nq), &hist))) return rc;
+    if ((rc = batch_topk_impl(h, db, queries, qoffsets, nq, sc, k, keys.data(), hist))) return rc;
     const int32_t m = static_cast<int32_t>(std::min<int64_t>(k, db->n));
     // second: the rows of all nq x m pairs, one launch sequence
     const size_t np = static_cast<size_t>(nq) * static_cast<size_t>(m);
@@ -2735,21 +2824,115 @@ int sw_scan_batch_hits(sw_handle* h, const sw_db* db, const uint8_t* queries, co
         return rc;
     for (int32_t q = 0; q < nq && m > 0; ++q)
         std::memcpy(out + static_cast<size_t>(q) * k, rows.data() + static_cast<size_t>(q) * m, static_cast<size_t>(m) * sizeof(sw_hit));
+    for (int32_t q = 0; q < nq && with_sig; ++q) {
+        sw_calib c;
+        calib_of(db, hist + static_cast<size_t>(q) * swcalib::kCells,
+                 static_cast<int32_t>(qoffsets[q + 1] - qoffsets[q]), &c);
+        for (int32_t i = 0; i < m; ++i) {
+            const sw_hit& r = rows[static_cast<size_t>(q) * m + i];
+            swcalib::significance(c, r.score, r.s_len, &sig[static_cast<size_t>(q) * k + i]);
+        }
+        if (calib) calib[q] = c;
+    }
     *nhits = m;
     return check_fault(h);
 }
 
-int sw_scan_hits(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc, int32_t k,
-                 sw_hit* out, int32_t* nhits) {
+// sw_scan_hits; sig (nullable, [k]) and calib (nullable): its _sig form.
+int scan_hits_impl(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc, int32_t k,
+                   sw_hit* out, int32_t* nhits, sw_sig* sig, sw_calib* calib) {
     if (!h || !db || !out || !nhits || k <= 0 || k > 4096) return fail(SW_E_INVALID, "bad argument (1 <= k <= 4096)");
     *nhits = 0;
     std::vector<int64_t> keys(static_cast<size_t>(k));
-    if (int rc = scan_topk_host(h, db, seq_src(query, qlen, sc), k, keys.data())) return rc;
+    uint32_t* hist = nullptr;
+    if (sig)
+        if (int rc = ensure_hist_host(h, 1, &hist)) return rc;
+    if (int rc = scan_topk_host(h, db, seq_src(query, qlen, sc), k, keys.data(), hist)) return rc;
     const int32_t m = static_cast<int32_t>(std::min<int64_t>(k, db->n));
     std::vector<int32_t> ids(static_cast<size_t>(m));
     for (int32_t i = 0; i < m; ++i) ids[i] = static_cast<int32_t>(0x7fffffff - (keys[i] & 0xffffffffll));
     if (int rc = hits_impl(h, db, query, qlen, sc, ids.data(), m, out)) return rc;
+    if (sig) {
+        sw_calib c;
+        calib_of(db, hist, qlen, &c);
+        for (int32_t i = 0; i < m; ++i) swcalib::significance(c, out[i].score, out[i].s_len, &sig[i]);
+        if (calib) *calib = c;
+    }
     *nhits = m;
+    return SW_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sw_scan_batch_hits(sw_handle* h, const sw_db* db, const uint8_t* queries, const int64_t* qoffsets, int32_t nq,
+                       const sw_scoring* sc, int32_t k, sw_hit* out, int32_t* nhits) {
+    return batch_hits_impl(h, db, queries, qoffsets, nq, sc, k, out, nhits, false, nullptr, nullptr);
+}
+
+int sw_scan_batch_hits_sig(sw_handle* h, const sw_db* db, const uint8_t* queries, const int64_t* qoffsets, int32_t nq,
+                           const sw_scoring* sc, int32_t k, sw_hit* out, sw_sig* sig, int32_t* nhits,
+                           sw_calib* calib) {
+    return batch_hits_impl(h, db, queries, qoffsets, nq, sc, k, out, nhits, true, sig, calib);
+}
+
+int sw_scan_hits(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc, int32_t k,
+                 sw_hit* out, int32_t* nhits) {
+    return scan_hits_impl(h, db, query, qlen, sc, k, out, nhits, nullptr, nullptr);
+}
+
+int sw_scan_hits_sig(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
+                     int32_t k, sw_hit* out, sw_sig* sig, int32_t* nhits, sw_calib* calib) {
+    if (!sig) return fail(SW_E_INVALID, "null argument");
+    return scan_hits_impl(h, db, query, qlen, sc, k, out, nhits, sig, calib);
+}
+
+// ---- the calibration alone (sw_calib.h) -------------------------------------
+int sw_score_hist_device(sw_handle* h, const sw_db* cdb, const int32_t* scores_dev, uint32_t* hist_dev) {
+    sw_db* db = const_cast<sw_db*>(cdb);
+    if (!h || !db || !hist_dev || (db->n > 0 && !scores_dev)) return fail(SW_E_INVALID, "null argument");
+    if (db->h != h) return fail(SW_E_INVALID, "the database belongs to another handle");
+    int rc;
+    if ((rc = check_fault(h))) return rc;
+    HIPCHECK(hipSetDevice(h->device));
+    if (!db->lay.built && (rc = build_db(db))) return rc;
+    return hist_after(h, db, scores_dev, hist_dev);
+}
+
+int sw_score_hist(sw_handle* h, const sw_db* db, const int32_t* scores_dev, uint32_t* hist_host) {
+    if (!h || !hist_host) return fail(SW_E_INVALID, "null argument");
+    HIPCHECK(hipSetDevice(h->device));
+    if (!h->d_hist.get()) HIPCHECK(swk::dev_alloc(h->d_hist, swcalib::kCells * sizeof(uint32_t)));
+    if (int rc = sw_score_hist_device(h, db, scores_dev, h->d_hist.get())) return rc;
+    HIPCHECK(hipMemcpyAsync(hist_host, h->d_hist.get(), swcalib::kCells * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                            h->stream.get()));
+    HIPCHECK(hipStreamSynchronize(h->stream.get()));
+    return check_fault(h);
+}
+
+int sw_calib_fit(const uint32_t* hist, int32_t qlen, sw_calib* out) {
+    if (!hist || !out || qlen < 0) return fail(SW_E_INVALID, "null argument");
+    swcalib::fit(hist, qlen, out);
+    return SW_OK;
+}
+
+int sw_calib_sig(const sw_calib* calib, int32_t score, int32_t slen, sw_sig* out) {
+    if (!calib || !out) return fail(SW_E_INVALID, "null argument");
+    if (calib->size != static_cast<int32_t>(sizeof(sw_calib)))
+        return fail(SW_E_INVALID, "sw_calib.size is not this library's (use sw_calib_fit)");
+    swcalib::significance(*calib, score, slen, out);
+    return SW_OK;
+}
+
+int sw_scan_pssm_topk_calib(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open, int32_t gap_extend,
+                            int32_t k, int64_t* keys_host, sw_calib* calib) {
+    if (!calib) return fail(SW_E_INVALID, "null argument");
+    if (int rc = check_pssm(h, p, gap_open, gap_extend)) return rc;
+    if (!db) return fail(SW_E_INVALID, "null argument");
+    uint32_t* hist = nullptr;
+    if (int rc = ensure_hist_host(h, 1, &hist)) return rc;
+    if (int rc = scan_topk_host(h, db, pssm_src(p, gap_open, gap_extend), k, keys_host, hist)) return rc;
+    calib_of(db, hist, p->qlen, calib);
     return SW_OK;
 }
 

@@ -516,4 +516,11 @@ struct TopkSrc {
 size_t topk_workspace_bytes(int64_t n, int k);
 hipError_t launch_topk(const TopkSrc& src, int64_t n, int k, int64_t* out, int64_t* work, hipStream_t s);
 
+// The calibration's count table (sw_calib.hip): subject g of [0, n), of length
+// slen[g] and score scores[rid ? rid[g] : g], adds 1 to
+// hist[length_bin][score column] (uint32 [128][512], sw_calib.h; zeroed by the
+// caller); a subject of length 0 is not counted.
+hipError_t launch_score_hist(const int32_t* scores, const int32_t* rid, const int32_t* slen, int64_t n,
+                             uint32_t* hist, hipStream_t s);
+
 }  // namespace swk

@@ -548,7 +548,9 @@ std::vector<seqid_score> smith_waterman_cuda_topk(FASTAQuery& query, FASTADataba
     return out;
 }
 
-std::vector<sw_hit> smith_waterman_cuda_hits(FASTAQuery& query, FASTADatabase& db, int k) {
+namespace {
+// smith_waterman_cuda_hits; sig (nullable): its _sig form (sw_scan_hits_sig).
+std::vector<sw_hit> hits_call(FASTAQuery& query, FASTADatabase& db, int k, std::vector<sw_sig>* sig, sw_calib* calib) {
     if (k < 1 || k > 4096) throw std::invalid_argument("the hit table needs 1 <= k <= 4096");
     std::lock_guard<std::mutex> lock(g_mu);
     // coordinates are those of the sequences as written: no '/' padding of
@@ -572,12 +574,27 @@ std::vector<sw_hit> smith_waterman_cuda_hits(FASTAQuery& query, FASTADatabase& d
     g_timing.upload_s = now_s() - t0;
     t0 = now_s();
     int32_t nhits = 0;
-    const int rc = sw_scan_hits(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, k, out.data(), &nhits);
+    if (sig) sig->assign(static_cast<size_t>(k), sw_sig{});
+    const int rc = sig ? sw_scan_hits_sig(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, k, out.data(),
+                                          sig->data(), &nhits, calib)
+                       : sw_scan_hits(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, k, out.data(), &nhits);
     g_timing.scan_s = now_s() - t0;
     sw_db_free(sdb);
-    check(rc, "sw_scan_hits");
+    check(rc, sig ? "sw_scan_hits_sig" : "sw_scan_hits");
     out.resize(static_cast<size_t>(nhits));
+    if (sig) sig->resize(static_cast<size_t>(nhits));
     return out;
+}
+}  // namespace
+
+std::vector<sw_hit> smith_waterman_cuda_hits(FASTAQuery& query, FASTADatabase& db, int k) {
+    return hits_call(query, db, k, nullptr, nullptr);
+}
+
+std::vector<sw_hit> smith_waterman_cuda_hits_sig(FASTAQuery& query, FASTADatabase& db, int k, std::vector<sw_sig>* sig,
+                                                 sw_calib* calib) {
+    if (!sig) throw std::invalid_argument("smith_waterman_cuda_hits_sig needs a vector for the significances");
+    return hits_call(query, db, k, sig, calib);
 }
 
 bool sw_solver_read_queries(const std::string& path, std::vector<std::string>* names, std::vector<std::string>* seqs,
@@ -674,6 +691,30 @@ std::vector<std::vector<sw_hit>> smith_waterman_cuda_batch_hits(const std::vecto
     std::vector<std::vector<sw_hit>> out(seqs.size());
     for (size_t q = 0; q < seqs.size(); ++q)
         out[q].assign(rows.begin() + static_cast<int64_t>(q) * k, rows.begin() + static_cast<int64_t>(q) * k + nhits);
+    return out;
+}
+
+std::vector<std::vector<sw_hit>> smith_waterman_cuda_batch_hits_sig(const std::vector<std::string>& seqs,
+                                                                    FASTADatabase& db, int k,
+                                                                    std::vector<std::vector<sw_sig>>* sig,
+                                                                    std::vector<sw_calib>* calib) {
+    if (!sig || !calib) throw std::invalid_argument("smith_waterman_cuda_batch_hits_sig needs its two output vectors");
+    const size_t kk = static_cast<size_t>(std::max(k, 0));
+    std::vector<sw_hit> rows(seqs.size() * kk);
+    std::vector<sw_sig> sigs(seqs.size() * kk);
+    calib->assign(seqs.size(), sw_calib{});
+    int32_t nhits = 0;
+    batch_call(seqs, db, k, "sw_scan_batch_hits_sig",
+               [&](sw_handle* h, sw_db* sdb, const uint8_t* qc, const int64_t* qoffs, int32_t nq, const sw_scoring* sc) {
+                   return sw_scan_batch_hits_sig(h, sdb, qc, qoffs, nq, sc, k, rows.data(), sigs.data(), &nhits,
+                                                 calib->data());
+               });
+    std::vector<std::vector<sw_hit>> out(seqs.size());
+    sig->assign(seqs.size(), std::vector<sw_sig>());
+    for (size_t q = 0; q < seqs.size(); ++q) {
+        out[q].assign(rows.begin() + static_cast<int64_t>(q) * k, rows.begin() + static_cast<int64_t>(q) * k + nhits);
+        (*sig)[q].assign(sigs.begin() + static_cast<int64_t>(q) * k, sigs.begin() + static_cast<int64_t>(q) * k + nhits);
+    }
     return out;
 }
 

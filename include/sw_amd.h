@@ -434,8 +434,8 @@ SW_API int sw_align(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t
  *                  are not written), *nhits = min(k, subjects), the same
  *                  for every query.  Two host synchronisations per call,
  *                  whatever nq is.
- * Out of scope: the PSSM forms, sw_group_*, E-values and bit scores, and
- * the ops string (that is sw_align's job).                                */
+ * Out of scope: the PSSM forms, sw_group_*, and the ops string (that is
+ * sw_align's job).  E-values and bit scores: the _sig forms below.        */
 typedef struct sw_hit {
     int32_t id, score;
     int32_t q_begin, q_end, s_begin, s_end;   /* 1-based, inclusive, as sw_alignment */
@@ -459,6 +459,97 @@ SW_API int sw_hit_stats_batch(sw_handle* h, const sw_db* db, const uint8_t* quer
 SW_API int sw_scan_batch_hits(sw_handle* h, const sw_db* db, const uint8_t* queries,
                               const int64_t* qoffsets, int32_t nq, const sw_scoring* sc,
                               int32_t k, sw_hit* out, int32_t* nhits);
+
+/* ---- E-values and bit scores: per-scan calibration (0.5.0) -----------------
+ * The caller may pass any matrix, any gap pair and a PSSM, so no table of
+ * Karlin-Altschul constants can serve; the significance of a hit is instead
+ * calibrated on the scan's own scores, as SSEARCH does: regress the score on
+ * ln(subject length) over the whole database, trim the related sequences,
+ * and turn a hit's z-score into an extreme-value E-value.  The scores are in
+ * HBM when the ranking runs: one more device pass counts them into a small
+ * integer table that comes down beside the keys.
+ *
+ * Length bin of a subject of length L >= 1 (integer only): e = floor(log2 L),
+ *   f = the two bits below L's leading bit ((L >> (e-2)) & 3 for e >= 2, else
+ *   (L << (2-e)) & 3), b = 4e + f; L = 1, 2, 3, 4, 5, 7, 8 give 0, 4, 6, 8, 9,
+ *   11, 12; b < 124.  The bin's abscissa is x_b = ln(2^e (1 + (f + 0.5)/4)).
+ * Table uint32 hist[SW_CALIB_LBINS][SW_CALIB_SBINS]: every SUBJECT of the
+ *   database (not every score slot) adds 1 at [b][min(max(score, 0), 511)]; a
+ *   subject of length 0 is not counted.  Column 511 is the clip column and
+ *   never enters the fit.  The table does not depend on the long threshold.
+ * Fit (host, doubles) over the cells (b, s), s < 511, with weight hist[b][s]:
+ *   weighted least squares of s on x_b gives the slope c and the intercept a;
+ *   sigma^2 = sum w r^2 / (W - 2), r = s - a - c x_b.  Cells with |r / sigma|
+ *   > 5 under the current a, c, sigma are dropped and the rest refitted, every
+ *   cell being tested again under the LATEST fit, until the kept set does not
+ *   change or 8 fits have run.  fits = regressions completed, n_fit = subjects
+ *   in the last one, n_db = subjects counted, n_clipped = those in column 511.
+ * Status bits:
+ *   SW_CALIB_CLIPPED    the clip column holds more than 1 % of the counted
+ *                       subjects (scores that grow with length: no local-
+ *                       alignment statistic exists under such a scoring);
+ *   SW_CALIB_FEW        fewer than 3 occupied length bins or fewer than 500
+ *                       subjects were kept;
+ *   SW_CALIB_DEGENERATE W < 3, fewer than two length bins (zero x-variance),
+ *                       or sigma == 0: then c = 0, a = the kept scores' mean,
+ *                       sigma = 0, every E-value is n_db and every bit score 0.
+ * Significance of a hit of score s against a subject of length L (its own
+ *   ln L, not its bin's):  z = (s - a - c ln L) / sigma,
+ *   E = n_db (1 - exp(-exp(-(pi/sqrt 6) z - gamma)))  (through expm1),
+ *   bits = ((pi/sqrt 6) z + gamma + ln(qlen L)) / ln 2,  gamma = Euler's constant.
+ *   L = 0, a score <= 0 or qlen = 0 give E = n_db, bits = 0, z = 0.
+ *
+ *   sw_score_hist_device : the table of scores_dev (max_id + 1 slots, as a
+ *                  scan wrote them) into hist_dev (device, 256 KB): a memset
+ *                  and one kernel, asynchronous on the handle's stream.  The
+ *                  per-subject length array it reads is uploaded on first use.
+ *   sw_score_hist : the same into host memory; synchronous.
+ *   sw_calib_fit, sw_calib_sig : the fit and the significance above; host
+ *                  only, no handle.  sw_calib_fit sets n_skipped to 0 (a table
+ *                  does not hold the zero-length subjects); the scan forms
+ *                  below set it.
+ *   sw_scan_hits_sig, sw_scan_batch_hits_sig : sw_scan_hits and
+ *                  sw_scan_batch_hits with sig[i] = sw_calib_sig(calib, row i's
+ *                  score, row i's s_len) beside every row and the scan's
+ *                  calibration in *calib (calib[nq], sig[nq][k] for the batch;
+ *                  calib may be NULL).  The table's launch follows every stage
+ *                  that writes that query's scores, its rescue tail included,
+ *                  and precedes the next query's scan; the tables come down
+ *                  with the keys: the batch keeps its two host synchronisations.
+ *   sw_scan_pssm_topk_calib : sw_scan_pssm_topk and the scan's calibration
+ *                  (there is no PSSM hit table: the caller applies sw_calib_sig
+ *                  to the keys' scores and sw_db_subjects' lengths).
+ * Out of scope: sw_group_*, composition-based score adjustment, and a search
+ * space other than the database scanned (n_db is its subject count).        */
+#define SW_CALIB_LBINS 128
+#define SW_CALIB_SBINS 512
+#define SW_CALIB_CLIPPED 1
+#define SW_CALIB_FEW 2
+#define SW_CALIB_DEGENERATE 4
+typedef struct sw_calib {
+    int32_t size;        /* sizeof(sw_calib), set by sw_calib_fit (ABI check) */
+    int32_t status;      /* SW_CALIB_* bits */
+    int32_t qlen;        /* the query's length (the bit score's search space) */
+    int32_t fits;        /* regressions completed (0: degenerate at once) */
+    int64_t n_db;        /* subjects counted */
+    int64_t n_fit;       /* subjects in the last fit */
+    int64_t n_clipped;   /* subjects in the clip column */
+    int64_t n_skipped;   /* zero-length subjects (not counted) */
+    double a, c, sigma;  /* score = a + c ln L, residual standard deviation */
+} sw_calib;
+typedef struct sw_sig {
+    double evalue, bits, z;
+} sw_sig;
+SW_API int sw_score_hist_device(sw_handle* h, const sw_db* db, const int32_t* scores_dev, uint32_t* hist_dev);
+SW_API int sw_score_hist(sw_handle* h, const sw_db* db, const int32_t* scores_dev, uint32_t* hist_host);
+SW_API int sw_calib_fit(const uint32_t* hist, int32_t qlen, sw_calib* out);
+SW_API int sw_calib_sig(const sw_calib* calib, int32_t score, int32_t slen, sw_sig* out);
+SW_API int sw_scan_hits_sig(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen,
+                            const sw_scoring* sc, int32_t k, sw_hit* out, sw_sig* sig, int32_t* nhits,
+                            sw_calib* calib);
+SW_API int sw_scan_batch_hits_sig(sw_handle* h, const sw_db* db, const uint8_t* queries,
+                                  const int64_t* qoffsets, int32_t nq, const sw_scoring* sc, int32_t k,
+                                  sw_hit* out, sw_sig* sig, int32_t* nhits, sw_calib* calib);
 
 /* ---- profile (PSSM) queries ------------------------------------------------
  * A position-specific scoring matrix in the place of a query: a [qlen][25]
@@ -495,6 +586,9 @@ SW_API int sw_scan_pssm_topk(sw_handle* h, const sw_db* db, const sw_pssm* p, in
 SW_API int sw_align_pssm(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open,
                          int32_t gap_extend, const int32_t* ids, int32_t n, sw_alignment* out,
                          char* ops, int64_t ops_stride);
+/* sw_scan_pssm_topk and the scan's calibration (see "E-values and bit scores"). */
+SW_API int sw_scan_pssm_topk_calib(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open,
+                                   int32_t gap_extend, int32_t k, int64_t* keys_host, sw_calib* calib);
 
 /* ---- single pair ---------------------------------------------------------
  * One query against one subject on the GPU (wavefront kernel); the GPU

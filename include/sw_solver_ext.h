@@ -77,6 +77,11 @@ std::vector<seqid_score> smith_waterman_cuda_topk(FASTAQuery& query, FASTADataba
  * One GPU.  Throws std::invalid_argument for another k or a subject without
  * a record id. */
 std::vector<sw_hit> smith_waterman_cuda_hits(FASTAQuery& query, FASTADatabase& db, int k);
+/* The same with each row's E-value, bit score and z-score in (*sig)[i] and
+ * the scan's calibration in *calib (may be NULL), from the scan's own scores
+ * (sw_amd.h sw_scan_hits_sig; `main --hits K --evalue`). */
+std::vector<sw_hit> smith_waterman_cuda_hits_sig(FASTAQuery& query, FASTADatabase& db, int k, std::vector<sw_sig>* sig,
+                                                 sw_calib* calib);
 
 /* Batches of queries (sw_amd.h sw_scan_batch_topk / sw_scan_batch_hits;
  * `main --queries FILE`).  sw_solver_read_queries reads a multi-record FASTA
@@ -97,6 +102,12 @@ std::vector<std::vector<seqid_score> > smith_waterman_cuda_batch_topk(const std:
                                                                       FASTADatabase& db, int k);
 std::vector<std::vector<sw_hit> > smith_waterman_cuda_batch_hits(const std::vector<std::string>& seqs,
                                                                  FASTADatabase& db, int k);
+/* The same with every row's significance in (*sig)[query][i] and every
+ * query's calibration in (*calib)[query] (sw_amd.h sw_scan_batch_hits_sig). */
+std::vector<std::vector<sw_hit> > smith_waterman_cuda_batch_hits_sig(const std::vector<std::string>& seqs,
+                                                                     FASTADatabase& db, int k,
+                                                                     std::vector<std::vector<sw_sig> >* sig,
+                                                                     std::vector<sw_calib>* calib);
 
 /* Profile (PSSM) queries (sw_amd.h sw_pssm_*; `main --pssm FILE`).
  * sw_solver_read_pssm reads a text PSSM into rows ([positions][25] int8 in
