@@ -620,26 +620,42 @@ class Database:
                                   out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         return out
 
-    def align(self, query_codes, ids, matrix=None, gap=2, gap_extend=None):
+    def _ops_buffer(self, qlen, n, ops_stride, ops):
+        """(buffer or None, stride) of an align call: ops_stride None sizes a
+        slot to the longest possible path, ops False passes no buffer."""
+        stride = qlen + int(self.stats()["max_length"]) + 1 if ops_stride is None else int(ops_stride)
+        return (ctypes.create_string_buffer(max(n, 1) * stride) if ops else None), stride
+
+    @staticmethod
+    def _alignments(out, n, buf, stride, with_len):
+        res = []
+        for k in range(n):
+            a = out[k]
+            al = {"score": a.score, "q_begin": a.q_begin, "q_end": a.q_end, "s_begin": a.s_begin, "s_end": a.s_end,
+                  "ops": None if buf is None else buf.raw[k * stride: k * stride + min(a.ops_len, stride)].decode()}
+            if with_len:
+                al["ops_len"] = a.ops_len
+            res.append(al)
+        return res
+
+    def align(self, query_codes, ids, matrix=None, gap=2, gap_extend=None, ops_stride=None, ops=True):
         """Traceback of the query against the subjects with these result ids
         (sw_align: cpu.cpp's tie rules for a linear gap; gap_extend != gap: the
         affine extension of them, include/sw_amd.h).  Returns a list of dicts
-        {score, q_begin, q_end, s_begin, s_end, ops} like the oracle's align."""
+        {score, q_begin, q_end, s_begin, s_end, ops} like the oracle's align.
+        ops_stride: bytes per hit of the ops buffer (None: the longest possible
+        path fits); a shorter slot holds the path's first ops_stride ops.
+        ops=False passes no buffer ("ops": None).  With either, a dict also
+        has "ops_len", the full path length."""
         q, qp = _u8(query_codes)
         idv = np.ascontiguousarray(ids, dtype=np.int32)
         n = len(idv)
         sc = _ScoringArg(matrix, gap, gap if gap_extend is None else gap_extend)
         out = (Alignment * max(n, 1))()
-        stride = len(q) + int(self.stats()["max_length"]) + 1
-        buf = ctypes.create_string_buffer(max(n, 1) * stride)
+        buf, stride = self._ops_buffer(len(q), n, ops_stride, ops)
         _check(lib().sw_align(self.handle.ptr, self._d, qp, len(q), sc.ptr(),
                               idv.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n, out, buf, stride))
-        res = []
-        for k in range(n):
-            a = out[k]
-            res.append({"score": a.score, "q_begin": a.q_begin, "q_end": a.q_end, "s_begin": a.s_begin,
-                        "s_end": a.s_end, "ops": buf.raw[k * stride: k * stride + a.ops_len].decode()})
-        return res
+        return self._alignments(out, n, buf, stride, ops_stride is not None or not ops)
 
     def hit_stats(self, query_codes, ids, matrix=None, gap=2, gap_extend=None):
         """The hit table's rows for the subjects with these result ids
@@ -726,22 +742,17 @@ class Database:
                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         return out
 
-    def align_pssm(self, pssm, ids, gap=2, gap_extend=None):
+    def align_pssm(self, pssm, ids, gap=2, gap_extend=None, ops_stride=None, ops=True):
         """Traceback of a Pssm against the subjects with these result ids
-        (sw_align_pssm; the tie rules and the result of align)."""
+        (sw_align_pssm; the tie rules, the result and the ops arguments of
+        align)."""
         idv = np.ascontiguousarray(ids, dtype=np.int32)
         n = len(idv)
         out = (Alignment * max(n, 1))()
-        stride = len(pssm) + int(self.stats()["max_length"]) + 1
-        buf = ctypes.create_string_buffer(max(n, 1) * stride)
+        buf, stride = self._ops_buffer(len(pssm), n, ops_stride, ops)
         _check(lib().sw_align_pssm(self.handle.ptr, self._d, pssm.ptr, gap, gap if gap_extend is None else gap_extend,
                                    idv.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n, out, buf, stride))
-        res = []
-        for k in range(n):
-            a = out[k]
-            res.append({"score": a.score, "q_begin": a.q_begin, "q_end": a.q_end, "s_begin": a.s_begin,
-                        "s_end": a.s_end, "ops": buf.raw[k * stride: k * stride + a.ops_len].decode()})
-        return res
+        return self._alignments(out, n, buf, stride, ops_stride is not None or not ops)
 
     @staticmethod
     def _cat(queries):

@@ -47,44 +47,48 @@ __device__ __forceinline__ bool better(const Best& x, const Best& y) {
 
 // The walk back from the best cell (thread 0), both gap models: H's source
 // in bits 0-1 of a direction byte, E / F extending in bits 2 / 3 (always 0
-// under linear gaps, where every E / F opens).
+// under linear gaps, where every E / F opens).  The walk meets the path's
+// last op first, so it runs twice when ops are wanted: once to count the
+// path and find the begin cell, then again storing step n (from the end) at
+// ops[len - 1 - n] where that lies inside the slot: a slot shorter than the
+// path holds the path's first ops_stride ops, from the begin cell.
 __device__ void align_walk(const AlignArgs& a, const Best& bb, const uint8_t* T, int W1, int hit) {
-    int i = bb.i, j = bb.j, state = 0;  // 0: H, 1: in an E run (left), 2: in an F run (up)
-    int64_t n = 0;
     char* ops = a.ops ? a.ops + static_cast<int64_t>(hit) * a.ops_stride : nullptr;
-    while (i > 0 && j > 0) {
-        const int t = T[static_cast<int64_t>(i + j) * W1 + i];
-        char op;
-        if (state == 0) {
-            const int src = t & 3;
-            if (src == 0) break;  // a zero cell (H = 0 has no source)
-            if (src != 3) {
-                state = src;
-                continue;
+    int i = 0, j = 0;
+    int64_t len = 0;
+    for (int pass = 0; pass < (ops ? 2 : 1); ++pass) {
+        int state = 0;  // 0: H, 1: in an E run (left), 2: in an F run (up)
+        int64_t n = 0;
+        i = bb.i;
+        j = bb.j;
+        while (i > 0 && j > 0) {
+            const int t = T[static_cast<int64_t>(i + j) * W1 + i];
+            char op;
+            if (state == 0) {
+                const int src = t & 3;
+                if (src == 0) break;  // a zero cell (H = 0 has no source)
+                if (src != 3) {
+                    state = src;
+                    continue;
+                }
+                op = 'M';
+                --i;
+                --j;
+            } else if (state == 1) {
+                op = 'D';
+                state = (t & 4) ? 1 : 0;
+                --j;
+            } else {
+                op = 'I';
+                state = (t & 8) ? 2 : 0;
+                --i;
             }
-            op = 'M';
-            --i;
-            --j;
-        } else if (state == 1) {
-            op = 'D';
-            state = (t & 4) ? 1 : 0;
-            --j;
-        } else {
-            op = 'I';
-            state = (t & 8) ? 2 : 0;
-            --i;
+            if (pass && len - 1 - n < a.ops_stride) ops[len - 1 - n] = op;
+            ++n;
         }
-        if (ops && n < a.ops_stride) ops[n] = op;
-        ++n;
+        len = n;
     }
-    if (ops) {
-        const int64_t m = n < a.ops_stride ? n : a.ops_stride;
-        for (int64_t k = 0; k < m / 2; ++k) {
-            const char c = ops[k];
-            ops[k] = ops[m - 1 - k];
-            ops[m - 1 - k] = c;
-        }
-    }
+    const int64_t n = len;
     int32_t* r = a.out + static_cast<int64_t>(hit) * 6;
     r[0] = bb.h;
     r[1] = i + 1;  // q_begin (1-based)

@@ -2487,19 +2487,15 @@ int align_impl(sw_handle* h, const sw_db* cdb, const QuerySrc& src, const int32_
     if (n == 0 || qlen == 0) return SW_OK;
     HIPCHECK(hipSetDevice(h->device));
     auto slen_of = [&](int64_t k) { return db->h_offsets[k + 1] - db->h_offsets[k]; };
-    // groups of hits whose direction arrays fit a 1 GiB budget
+    // groups of hits whose direction arrays fit the budget (swplan::align_groups)
     const int64_t W1 = static_cast<int64_t>(qlen) + 1;
+    std::vector<int64_t> slens(static_cast<size_t>(n));
+    for (int32_t k = 0; k < n; ++k) slens[k] = slen_of(sidx[k]);
     int32_t k0 = 0;
-    while (k0 < n) {
-        int64_t bytes = 0, res = 0;
-        int32_t k1 = k0;
-        while (k1 < n) {
-            const int64_t b = (qlen + slen_of(sidx[k1]) + 1) * W1;
-            if (k1 > k0 && bytes + b > (int64_t(1) << 30)) break;
-            bytes += b;
-            res += slen_of(sidx[k1]);
-            ++k1;
-        }
+    for (const int64_t end : swplan::align_groups(qlen, slens.data(), n)) {
+        const int32_t k1 = static_cast<int32_t>(end);
+        int64_t res = 0;
+        for (int32_t k = k0; k < k1; ++k) res += slens[k];
         const int32_t m = k1 - k0;
         std::vector<uint8_t> hsub(static_cast<size_t>(std::max<int64_t>(res, 1)));
         std::vector<int64_t> hoff(m + 1, 0), hdoff(m, 0);
@@ -2509,7 +2505,7 @@ int align_impl(sw_handle* h, const sw_db* cdb, const QuerySrc& src, const int32_
             subject_residues(db, src, hsub.data() + hoff[k]);
             hoff[k + 1] = hoff[k] + L;
             hdoff[k] = dacc;
-            dacc += (qlen + L + 1) * W1;
+            dacc += swplan::align_dirs_bytes(qlen, L);
         }
         std::vector<int32_t> hout(static_cast<size_t>(m) * 6);
         // this group's buffers (qlen, m >= 1: no empty one), released after the synchronise below

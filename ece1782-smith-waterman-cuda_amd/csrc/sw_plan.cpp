@@ -637,6 +637,26 @@ std::vector<int64_t> hits_groups(const int32_t* qlens, const int64_t* slens, int
     return ends;
 }
 
+int64_t align_dirs_bytes(int32_t qlen, int64_t slen) {
+    return (qlen + slen + 1) * (static_cast<int64_t>(qlen) + 1);
+}
+
+std::vector<int64_t> align_groups(int32_t qlen, const int64_t* slens, int64_t n, int64_t budget) {
+    std::vector<int64_t> ends;
+    int64_t bytes = 0, k0 = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t b = align_dirs_bytes(qlen, slens[k]);
+        if (k > k0 && bytes + b > budget) {
+            ends.push_back(k);
+            k0 = k;
+            bytes = 0;
+        }
+        bytes += b;
+    }
+    if (n > 0) ends.push_back(n);
+    return ends;
+}
+
 int64_t hits_cost(int32_t qlen, int64_t slen) {
     if (qlen <= 0 || slen <= 0) return 0;
     constexpr int64_t kWaveRows = swk::kLanes * swk::kHitsRowsPerLane;

@@ -192,4 +192,14 @@ int64_t hits_cost(int32_t qlen, int64_t slen);
 // order, so the longest wavefronts start in the first wave of workgroups.
 std::vector<int64_t> hits_order(const int32_t* qlens, const int64_t* slens, int64_t n);
 
+// The traceback's direction array (sw_align.hip): one byte per cell, stored
+// diagonal-major T[d][i], d in [0, qlen + slen], i in [0, qlen].
+int64_t align_dirs_bytes(int32_t qlen, int64_t slen);
+constexpr int64_t kAlignDirsBudget = int64_t(1) << 30;
+// Hits [ends[g - 1], ends[g]) (ends[-1] = 0) of one sw_align call run as one
+// launch: consecutive hits, in the caller's order, whose direction arrays fit
+// the budget; a single hit over the budget forms its own group.
+// ends.back() == n; empty for n == 0.
+std::vector<int64_t> align_groups(int32_t qlen, const int64_t* slens, int64_t n, int64_t budget = kAlignDirsBudget);
+
 }  // namespace swplan

@@ -379,8 +379,13 @@ SW_API int sw_scan_rank_device(sw_handle* h, const sw_db* db, const uint8_t* que
  * (optional, n x ops_stride bytes, not NUL-terminated) spells the path from
  * the begin cell: 'M' an aligned pair, 'I' a query residue against a gap,
  * 'D' a subject residue against a gap; ops_len is the full path length even
- * when it exceeds ops_stride.  Cost O(|q| x |subject|) per hit: meant for
- * the top hits of a scan (e.g. the ids from sw_topk).                     */
+ * when it exceeds ops_stride.  A slot shorter than its path holds the
+ * path's first ops_stride ops, so it replays from (q_begin, s_begin); bytes
+ * of a slot past min(ops_len, ops_stride) are unspecified.  ops == NULL:
+ * positions and ops_len only.  Hits run in launches whose direction arrays
+ * (one byte per cell) fit 1 GiB together (swplan::align_groups; a larger
+ * single hit runs alone).  Cost O(|q| x |subject|) per hit: meant for the
+ * top hits of a scan (e.g. the ids from sw_topk).                         */
 typedef struct sw_alignment {
     int32_t score;
     int32_t q_begin, q_end;

@@ -234,22 +234,27 @@ int swo_align_linear(const uint8_t* q, int qlen, const uint8_t* s, int slen,
             T[i * W + j] = t;
         }
     }
-    /* Walk back while the cell value is non-zero (cpu.cpp:80-103).  Ops are
-     * written end->start then reversed: 'M' aligned pair, 'I' query residue
-     * against a gap (move up), 'D' subject residue against a gap (move left). */
-    int i = bi, j = bj, n = 0;
-    while (i > 0 && j > 0 && H[i * W + j] != 0) {
-        unsigned char t = T[i * W + j];
-        char op;
-        if (t == 1) { op = 'D'; --j; }
-        else if (t == 2) { op = 'I'; --i; }
-        else if (t == 3) { op = 'M'; --i; --j; }
-        else break;
-        if (n < ops_cap) ops[n] = op;
-        ++n;
+    /* Walk back while the cell value is non-zero (cpu.cpp:80-103): 'M' aligned
+     * pair, 'I' query residue against a gap (move up), 'D' subject residue
+     * against a gap (move left).  The walk meets the last op first, so it runs
+     * twice: once to count, then storing step n at ops[len - 1 - n] where that
+     * is below ops_cap.  A short buffer holds the path's first ops_cap ops,
+     * from the begin cell. */
+    int i = 0, j = 0, n = 0;
+    for (int pass = 0; pass < 2; ++pass) { /* count, then store */
+        int len = n;
+        i = bi; j = bj; n = 0;
+        while (i > 0 && j > 0 && H[i * W + j] != 0) {
+            unsigned char t = T[i * W + j];
+            char op;
+            if (t == 1) { op = 'D'; --j; }
+            else if (t == 2) { op = 'I'; --i; }
+            else if (t == 3) { op = 'M'; --i; --j; }
+            else break;
+            if (pass && len - 1 - n < ops_cap) ops[len - 1 - n] = op;
+            ++n;
+        }
     }
-    int m = n < ops_cap ? n : ops_cap;
-    for (int k = 0; k < m / 2; ++k) { char c = ops[k]; ops[k] = ops[m - 1 - k]; ops[m - 1 - k] = c; }
     *ops_len = n;
     *q_end = bi; *s_end = bj;
     *q_begin = i + 1; *s_begin = j + 1;
@@ -305,29 +310,31 @@ int swo_align_affine(const uint8_t* q, int qlen, const uint8_t* s, int slen,
             T[i * W + j] = t;
         }
     }
-    int i = bi, j = bj, n = 0, state = 0; /* 0: H, 1: in an E run, 2: in an F run */
-    while (i > 0 && j > 0) {
-        unsigned char t = T[i * W + j];
-        char op;
-        if (state == 0) {
-            int src = t & 3;
-            if (src == 0 || H[i * W + j] == 0) break;
-            if (src == 3) { op = 'M'; --i; --j; }
-            else { state = src; continue; }
-        } else if (state == 1) {
-            op = 'D';
-            state = (t & 4) ? 1 : 0;
-            --j;
-        } else {
-            op = 'I';
-            state = (t & 8) ? 2 : 0;
-            --i;
+    int i = 0, j = 0, n = 0;
+    for (int pass = 0; pass < 2; ++pass) { /* count, then store (as swo_align_linear) */
+        int len = n, state = 0; /* 0: H, 1: in an E run, 2: in an F run */
+        i = bi; j = bj; n = 0;
+        while (i > 0 && j > 0) {
+            unsigned char t = T[i * W + j];
+            char op;
+            if (state == 0) {
+                int src = t & 3;
+                if (src == 0 || H[i * W + j] == 0) break;
+                if (src == 3) { op = 'M'; --i; --j; }
+                else { state = src; continue; }
+            } else if (state == 1) {
+                op = 'D';
+                state = (t & 4) ? 1 : 0;
+                --j;
+            } else {
+                op = 'I';
+                state = (t & 8) ? 2 : 0;
+                --i;
+            }
+            if (pass && len - 1 - n < ops_cap) ops[len - 1 - n] = op;
+            ++n;
         }
-        if (n < ops_cap) ops[n] = op;
-        ++n;
     }
-    int m = n < ops_cap ? n : ops_cap;
-    for (int k = 0; k < m / 2; ++k) { char c = ops[k]; ops[k] = ops[m - 1 - k]; ops[m - 1 - k] = c; }
     *ops_len = n;
     *q_end = bi; *s_end = bj;
     *q_begin = i + 1; *s_begin = j + 1;

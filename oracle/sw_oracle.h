@@ -71,7 +71,9 @@ void swo_scan(const uint8_t* q, int qlen, const uint8_t* res, const int64_t* off
 /* Optimal local alignment with traceback under the tie order of cpu.cpp:47-64
  * (strict '>' in order left, up, diagonal; first strict maximum cell,
  * cpu.cpp:66-70).  Linear gap only.  Writes the 1-based end cell and the
- * start cell (first aligned residue, 1-based) and the alignment length. */
+ * start cell (first aligned residue, 1-based) and the alignment length
+ * (*ops_len: the full path, whatever ops_cap); ops gets the path's first
+ * min(*ops_len, ops_cap) ops, from the start cell. */
 int swo_align_linear(const uint8_t* q, int qlen, const uint8_t* s, int slen,
                      const int8_t* mat, int gap, int* q_end, int* s_end,
                      int* q_begin, int* s_begin, char* ops, int ops_cap,

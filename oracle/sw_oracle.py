@@ -201,26 +201,32 @@ def scan(q, residues, offsets, mat=None, gap_open=2, gap_extend=2, nthreads=0):
     return out
 
 
-def align(q, s, mat=None, gap=2, gap_extend=None):
+def align(q, s, mat=None, gap=2, gap_extend=None, ops_cap=None):
     """Score + traceback under cpu.cpp's tie rules (oracle/sw_oracle.c
     swo_align_linear, cpu.cpp:47-108); with gap_extend != gap the affine
-    traceback swo_align_affine (this build's tie order).  Returns dict."""
+    traceback swo_align_affine (this build's tie order).  Returns dict.
+    ops_cap: the size of the ops buffer (None: the longest possible path
+    fits); the dict then also has "ops_len", the full path length, and "ops"
+    is the path's first min(ops_len, ops_cap) ops."""
     mat = matrix() if mat is None else mat
     q, qp = _u8(q)
     s, sp = _u8(s)
     m, mp = _mat_ptr(mat)
     ints = [ctypes.c_int() for _ in range(5)]
-    cap = len(q) + len(s) + 1
-    buf = ctypes.create_string_buffer(cap)
+    cap = len(q) + len(s) + 1 if ops_cap is None else int(ops_cap)
+    buf = ctypes.create_string_buffer(max(cap, 1))
     refs = [ctypes.byref(x) for x in ints[:4]]
     if gap_extend is None or gap_extend == gap:
         best = lib().swo_align_linear(qp, len(q), sp, len(s), mp, gap, *refs, buf, cap, ctypes.byref(ints[4]))
     else:
         best = lib().swo_align_affine(qp, len(q), sp, len(s), mp, gap, gap_extend, *refs, buf, cap,
                                       ctypes.byref(ints[4]))
-    return {"score": best, "q_end": ints[0].value, "s_end": ints[1].value,
-            "q_begin": ints[2].value, "s_begin": ints[3].value,
-            "ops": buf.raw[: ints[4].value].decode()}
+    al = {"score": best, "q_end": ints[0].value, "s_end": ints[1].value,
+          "q_begin": ints[2].value, "s_begin": ints[3].value,
+          "ops": buf.raw[: min(ints[4].value, cap)].decode()}
+    if ops_cap is not None:
+        al["ops_len"] = ints[4].value
+    return al
 
 
 def score_linear_py(q, s, mat, gap):

@@ -1,5 +1,7 @@
 """Expected hit-table rows (sw_hit, include/sw_amd.h), derived from the
-oracle's traceback: shared by tests/test_gpu_hits.py's cases.
+oracle's traceback: shared by tests/test_gpu_hits.py's cases; and the seam
+inputs (gap runs placed on chosen query rows), shared with
+tests/test_gpu_align_rules.py.
 
 A row is a function of the alignment oracle.align reports: its begin and end
 cells and its ops string.  identities and positives come from replaying the
@@ -49,3 +51,32 @@ def pack(subs):
     offs = np.zeros(len(subs) + 1, dtype=np.int64)
     offs[1:] = np.cumsum([len(s) for s in subs])
     return res, offs
+
+
+# no C, H, P, W (tests/seam_support.py): the 16 lowest diagonal entries
+ALPHABET = np.array([0, 1, 2, 3, 5, 6, 7, 9, 10, 11, 12, 13, 15, 16, 18, 19], dtype=np.uint8)
+
+
+def seam_query(n, seed):
+    """No residue twice in a row: beside a doubled residue a gap run splits for
+    free and can step round any one seam (tests/seam_support.py)."""
+    rng = np.random.default_rng(seed)
+    return ALPHABET[np.cumsum(rng.integers(1, len(ALPHABET), size=n)) % len(ALPHABET)]
+
+
+def seam_subjects(q, seams):
+    """Copies of q with L = 1, 2, 5 rows deleted (query rows against gaps: a
+    run down the column) or L columns inserted (a run along the row) so that
+    the run starts on, crosses and ends on each seam row."""
+    ins = np.random.default_rng(4711)
+    subs, seen = [], set()
+    for s in seams:
+        for L in (1, 2, 5):
+            for p in (s, s - 1, s - L + 1):
+                if p < 1 or p + L >= len(q) or (p, L) in seen:
+                    continue
+                seen.add((p, L))
+                subs.append(np.concatenate([q[:p], q[p + L:]]))
+                other = ALPHABET[(ALPHABET != q[p - 1]) & (ALPHABET != q[p])]
+                subs.append(np.concatenate([q[:p], other[ins.integers(0, len(other), size=L)], q[p:]]))
+    return subs

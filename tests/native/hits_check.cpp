@@ -10,7 +10,8 @@
 //   location  swpack::locate + swk::hit_residue_at against the bytes
 //             fill_block / fill_long write: every subject's residues are
 //             recovered from its location;
-//   groups    swplan::hits_scratch_bytes / hits_groups.
+//   groups    swplan::hits_scratch_bytes / hits_groups, and sw_align's swplan::align_dirs_bytes /
+//             align_groups.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -271,6 +272,58 @@ static void check_groups() {
     std::printf("groups: %lld bytes per column\n", (long long)per);
 }
 
+// ---- sw_align's groups -----------------------------------------------------------
+static void check_align_groups() {
+    CHECK(swplan::align_dirs_bytes(0, 0) == 1 && swplan::align_dirs_bytes(3, 5) == 9 * 4 &&
+              swplan::align_dirs_bytes(16383, 16385) == 536887296,
+          "(qlen + slen + 1) (qlen + 1) bytes per hit");
+    CHECK(swplan::align_dirs_bytes(1 << 20, int64_t(1) << 30) == ((int64_t(1) << 30) + (1 << 20) + 1) * ((1 << 20) + 1),
+          "64-bit sizes");
+    std::mt19937 rng(11);
+    int64_t multi = 0, alone = 0;
+    for (int round = 0; round < 200; ++round) {
+        const int64_t n = rng() % 40;
+        const int32_t q = 1 + rng() % 300;
+        const int64_t budget = swplan::align_dirs_bytes(q, 1 + rng() % 2000);
+        std::vector<int64_t> slens(static_cast<size_t>(n));
+        for (auto& s : slens) s = rng() % 10 == 0 ? 3000 + rng() % 3000 : rng() % 700;  // some alone over the budget
+        const std::vector<int64_t> ends = swplan::align_groups(q, slens.data(), n, budget);
+        CHECK((n == 0) == ends.empty() && (n == 0 || ends.back() == n), "align groups end at n");
+        int64_t k0 = 0;
+        for (const int64_t k1 : ends) {  // the groups tile [0, n) in order
+            CHECK(k1 > k0, "an empty align group");
+            int64_t bytes = 0;
+            for (int64_t k = k0; k < k1; ++k) bytes += swplan::align_dirs_bytes(q, slens[k]);
+            CHECK(bytes <= budget || k1 == k0 + 1, "an align group of %lld hits holds %lld bytes, budget %lld",
+                  (long long)(k1 - k0), (long long)bytes, (long long)budget);
+            // greedy: the next hit would not have fitted
+            if (k1 < n) CHECK(bytes + swplan::align_dirs_bytes(q, slens[k1]) > budget, "an align group closed early");
+            multi += k1 > k0 + 1;
+            alone += bytes > budget;
+            k0 = k1;
+        }
+    }
+    CHECK(multi > 100 && alone > 100, "the rounds reach groups of several hits (%lld) and over-budget hits (%lld)",
+          (long long)multi, (long long)alone);
+    // the exact fit: hits that fill the budget to the byte stay together, one byte less splits them
+    const int64_t fit[3] = {7, 12, 30};
+    const int64_t exact = swplan::align_dirs_bytes(9, 7) + swplan::align_dirs_bytes(9, 12) + swplan::align_dirs_bytes(9, 30);
+    std::vector<int64_t> ends = swplan::align_groups(9, fit, 3, exact);
+    CHECK(ends.size() == 1 && ends[0] == 3, "an exact fit is one group");
+    ends = swplan::align_groups(9, fit, 3, exact - 1);
+    CHECK(ends.size() == 2 && ends[0] == 2 && ends[1] == 3, "one byte under the exact fit splits before the last hit");
+    // a query of 16,383 against 16,385, 16,385 and 100 residues at the default budget: each of the
+    // long hits takes just over half of it
+    const int64_t three[3] = {16385, 16385, 100};
+    CHECK(2 * swplan::align_dirs_bytes(16383, 16385) > swplan::kAlignDirsBudget &&
+              swplan::align_dirs_bytes(16383, 16385) + swplan::align_dirs_bytes(16383, 100) <= swplan::kAlignDirsBudget,
+          "the three-hit case straddles the default budget");
+    ends = swplan::align_groups(16383, three, 3);
+    CHECK(ends.size() == 2 && ends[0] == 1 && ends[1] == 3, "the three-hit case groups as {0}, {1, 2}");
+    std::printf("align_groups: budget %lld, three-hit ends %lld %lld\n", (long long)swplan::kAlignDirsBudget,
+                ends.size() == 2 ? (long long)ends[0] : -1LL, ends.size() == 2 ? (long long)ends[1] : -1LL);
+}
+
 int main() {
     check_rules();
     for (int64_t n : {0, 1, 63, 64, 65, 129}) {
@@ -281,6 +334,7 @@ int main() {
         check_location(n, -1, "default");
     }
     check_groups();
+    check_align_groups();
     std::printf("chunk_rows: %d\n", swk::kHitsChunkRows);
     std::printf("rows_per_lane: %d\nwaves: %d\n", swk::kHitsRowsPerLane, swk::kHitsWaves);
     std::printf(failures ? "hits_check FAILED (%d)\n" : "hits_check ok\n", failures);

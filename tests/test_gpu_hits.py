@@ -9,16 +9,15 @@ import subprocess
 import numpy as np
 import pytest
 
+import align_support
 from conftest import GOLDEN, REPO
-from hits_support import FIELDS, expected, pack, row_of
+from hits_support import FIELDS, expected, pack, row_of, seam_query, seam_subjects
 
 pytestmark = pytest.mark.gpu
 LIB = os.path.join(REPO, "ece1782-smith-waterman-cuda_amd", "lib")
 
 # (matrix id, open, extend)
 SCORINGS = {"b50-linear-2": (0, 2, 2), "b62-11-1": (1, 11, 1), "b62-12-1": (1, 12, 1), "id3-linear-2": (2, 2, 2)}
-# no C, H, P, W (tests/seam_support.py): the 16 lowest diagonal entries
-ALPHABET = np.array([0, 1, 2, 3, 5, 6, 7, 9, 10, 11, 12, 13, 15, 16, 18, 19], dtype=np.uint8)
 
 
 def check_rows(oracle, got, q, subs, ids_of, mat, go, ge):
@@ -91,31 +90,6 @@ def test_layout_edges(sw, oracle, handle, threshold):
     db.close()
 
 
-def seam_query(n, seed):
-    """No residue twice in a row: beside a doubled residue a gap run splits for
-    free and can step round any one seam (tests/seam_support.py)."""
-    rng = np.random.default_rng(seed)
-    return ALPHABET[np.cumsum(rng.integers(1, len(ALPHABET), size=n)) % len(ALPHABET)]
-
-
-def seam_subjects(q, seams):
-    """Copies of q with L = 1, 2, 5 rows deleted (query rows against gaps: a
-    run down the column) or L columns inserted (a run along the row) so that
-    the run starts on, crosses and ends on each seam row."""
-    ins = np.random.default_rng(4711)
-    subs, seen = [], set()
-    for s in seams:
-        for L in (1, 2, 5):
-            for p in (s, s - 1, s - L + 1):
-                if p < 1 or p + L >= len(q) or (p, L) in seen:
-                    continue
-                seen.add((p, L))
-                subs.append(np.concatenate([q[:p], q[p + L:]]))
-                other = ALPHABET[(ALPHABET != q[p - 1]) & (ALPHABET != q[p])]
-                subs.append(np.concatenate([q[:p], other[ins.integers(0, len(other), size=L)], q[p:]]))
-    return subs
-
-
 @pytest.mark.parametrize("go,ge", [(5, 5), (12, 1)])
 @pytest.mark.parametrize("rows", ["C-1", "C", "C+1", "2C+3"])
 def test_seams(sw, oracle, handle, rows, go, ge):
@@ -157,6 +131,22 @@ def test_ties(sw, oracle, handle):
             q = rng.integers(0, 2, size=int(rng.integers(20, 61))).astype(np.uint8)
             check_rows(oracle, db.hit_stats(q, ids, m, go, ge), q, subs, [(i, i) for i in ids], m, go, ge)
         db.close()
+
+
+@pytest.mark.parametrize("name", sorted(align_support.SCORINGS))
+def test_tie_set(sw, oracle, handle, name):
+    """The traceback's tie set (tests/align_support.py; tests/
+    test_align_inputs.py shows that its pairs tell the tie rules apart, which
+    test_ties' scorings, with 2 gap >= |mismatch|, cannot for left before up):
+    every row from both layouts."""
+    mat, go, ge = align_support.scoring(name)
+    groups = align_support.TIE_GROUPS[align_support.SCORINGS[name][0]]
+    for thr in (4096, 8):
+        for q, subs in groups[::2] if thr == 8 else groups:
+            db = sw.Database(handle, *pack(subs), long_threshold=thr)
+            ids = list(range(len(subs)))
+            check_rows(oracle, db.hit_stats(q, ids, mat, go, ge), q, subs, [(i, i) for i in ids], mat, go, ge)
+            db.close()
 
 
 def test_size(sw, oracle, handle):

@@ -126,6 +126,7 @@ def test_topk_one_launch_sizes(sw, handle, n, k):
     d = torch.from_numpy(s).to(dev)
     for rep in range(2):
         out = torch.zeros(k, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()  # the fill runs on torch's stream, the top-K on the handle's (non-blocking)
         handle.topk_device(d.data_ptr(), n, k, out.data_ptr(), id_base=rep)
         torch.cuda.synchronize()
         want = _padded(sw.dist.local_topk(s, np.arange(n, dtype=np.int32) + rep, k), k)

@@ -5,7 +5,8 @@ scalar pass and compares every field with the row the oracle's traceback
 and tie-heavy pairs over 2 to 4 codes under six scorings; injects three
 faults that each must be noticed; recovers every subject's residues from its
 location (swpack::locate + swk::hit_residue_at) in the bytes the packer
-writes; and checks the scratch size and the grouping of hits.  The CLI's
+writes; and checks the scratch size and the grouping of hits, the hit
+table's and sw_align's.  The CLI's
 --hits checks run before any file is read, so they need no GPU."""
 import os
 import re
@@ -70,6 +71,15 @@ def test_every_subject_is_read_back_from_its_location(hits_check):
 @needs_hipcc
 def test_scratch_and_groups(hits_check):
     assert "groups: 64 bytes per column" in hits_check
+
+
+@needs_hipcc
+def test_align_groups(hits_check):
+    """swplan::align_groups (sw_align's launches): tiling, budget, greedy
+    maximality and the exact fit are CHECKed natively; a query of 16,383
+    against subjects of 16,385, 16,385 and 100 residues makes two launches at
+    the default budget (tests/test_gpu_align_rules.py runs that call)."""
+    assert "align_groups: budget %d, three-hit ends 1 3\n" % (1 << 30) in hits_check
 
 
 @needs_hipcc
