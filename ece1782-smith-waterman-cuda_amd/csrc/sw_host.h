@@ -1,4 +1,4 @@
-// sw_host.h — what the host driver (sw_capi.cpp, sw_group.cpp) shares and no
+// sw_host.h — what the host driver (sw_driver.h's units, sw_group.cpp) shares and no
 // kernel sees: the owners of HIP resources, their allocation helpers and the
 // error macro.  A HIP resource is a member or a local of owner type and is
 // released by its destructor; a raw pointer, event or stream is an alias

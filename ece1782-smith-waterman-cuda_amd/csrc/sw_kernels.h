@@ -1,5 +1,5 @@
-// sw_kernels.h — internal interface between the host code (the driver
-// sw_capi.cpp, the packer sw_pack.cpp, the planner sw_plan.cpp) and the
+// sw_kernels.h — internal interface between the host code (the driver's
+// units, sw_driver.h; the packer sw_pack.cpp, the planner sw_plan.cpp) and the
 // gfx950 kernels (sw_kernels.hip).  Not part of the public ABI.
 #pragma once
 
@@ -13,8 +13,7 @@
 namespace swk {
 
 // Record `msg` as this thread's sw_last_error() text and return `code`
-// (sw_capi.cpp; used by the other host translation units: sw_group.cpp,
-// sw_dbfile.cpp).
+// (sw_handle.cpp; used by every host translation unit).
 int set_error(int code, const std::string& msg);
 
 constexpr int kLanes = 64;        // one database subject per lane (wave64)

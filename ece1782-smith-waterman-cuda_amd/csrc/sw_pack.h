@@ -1,7 +1,7 @@
 // sw_pack.h — the packed database layout as pure host code (sw_pack.cpp): no
 // HIP call, no handle, so the layout every scan kernel, sw_synth_fill_* and
 // sw_align decode is checked on the CPU (tests/native/pack_check.cpp).
-// sw_capi.cpp's build_db asks for a Shape, allocates, and uploads what
+// sw_db.cpp's build_db asks for a Shape, allocates, and uploads what
 // fill_block / fill_long write:
 //   * subjects longest first, stable (file order within a length);
 //   * those longer than the threshold one after another, each start 64-byte

@@ -1,5 +1,5 @@
 // sw_parallel.h — the host code's one thread pool shape: a loop over indices
-// shared out to a few threads (sw_capi.cpp's copies and staged uploads,
+// shared out to a few threads (sw_db.cpp's copies and staged uploads,
 // sw_pack.cpp's lane tables).  No HIP.
 #pragma once
 

@@ -4,8 +4,8 @@
 // blocks run by wave pairs, quads, 3-wave groups or tail pairs, and the
 // longest-first work table of the merged launch (sw_scan_lpt) with its
 // duration estimates.  Plain host code over a read-only view of a database
-// (PlanDb); sw_capi.cpp owns the databases, caches the tables and uploads
-// them.  scan_plan (at the end) puts the policies together: the form one
+// (PlanDb); sw_db.cpp owns the databases, sw_capi.cpp caches the tables and
+// uploads them.  scan_plan (at the end) puts the policies together: the form one
 // scan takes, as a pure function of the database view, the query length,
 // the scoring and the two adaptive routes.
 #include "sw_plan.h"

@@ -4,7 +4,7 @@
 // (tests/test_plan.py).  scan_plan() is where the form of a scan is decided:
 // gap model, kernel shapes, rows per lane, block counts, merged launch or
 // not, and the names sw_last_kernel reports; sw_capi.cpp's scan_impl_body
-// only enqueues what the plan says.  sw_capi.cpp owns the databases and the
+// only enqueues what the plan says.  sw_db.cpp owns the databases and the
 // device copies of the tables.
 #pragma once
 
@@ -17,7 +17,7 @@
 
 namespace swplan {
 
-// What the policies read of a database (sw_capi.cpp plan_view: the counts
+// What the policies read of a database (sw_db.cpp plan_view: the counts
 // and tables of sw_db's swpack::Shape, sw_pack.h).
 struct PlanDb {
     int64_t n = 0;                        // subjects
@@ -122,7 +122,7 @@ struct ScanPlan {
     std::string kernel, intra_kernel;
 
     // The one runtime fact the plan cannot know: whether the merged launch
-    // obtained boundary rows of its own (sw_capi.cpp ensure_rbnd; lpt only).
+    // obtained boundary rows of its own (sw_db.cpp ensure_rbnd; lpt only).
     // With them it drains its rescue lists itself, the int32 long-subject
     // stage at the fp16 form's rows per lane: ri = ri2, qpad_intra (and
     // multi_intra, a function of the two) follow, the name gets "+drain".

@@ -2,7 +2,7 @@
 // (sw_dbfile.cpp): what write() stores read() gives back, and a file that is
 // cut, altered or not of this format is refused with the code and message
 // sw_db_load has always reported.  Linked from sw_dbfile.cpp alone: the
-// error sink swk::set_error (sw_capi.cpp's in the library) is this file's.
+// error sink swk::set_error (sw_handle.cpp's in the library) is this file's.
 // usage: dbfile_check SCRATCH_DIR.  Built and run by tests/test_dbfile.py.
 #include <cstdio>
 #include <cstring>

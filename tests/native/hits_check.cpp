@@ -203,7 +203,7 @@ static void check_location(int64_t n, int32_t threshold, const char* tname) {
     std::vector<uint8_t> inter(sh.total + 1, 0xee), longs(sh.ltotal + 1, 0xee);
     for (int64_t b = 0; b < sh.nblocks; ++b) swpack::fill_block(subj, sh, b, inter.data() + sh.blk_off[b]);
     for (int64_t k = 0; k < sh.nlong; ++k) swpack::fill_long(subj, sh, k, longs.data() + sh.loff[k]);
-    // position of each subject: what sw_capi.cpp rebuilds from length_order
+    // position of each subject: what sw_db.cpp's position_of rebuilds from length_order
     const std::vector<int64_t> order = swpack::length_order(offs.data(), n);
     int64_t recovered = 0;
     for (int64_t p = 0; p < n; ++p) {

@@ -5,6 +5,7 @@ implies (tests/hits_support.py) and, where a case says so, with the
 single-query calls.  The shapes are the smallest at which the mixed launch
 can go wrong: queries of 0, 1, one chunk +- 1 and three chunks side by side,
 two multi-chunk queries on one subject, an empty subject, duplicated pairs."""
+import ctypes
 import os
 import subprocess
 
@@ -274,3 +275,54 @@ def test_cli_queries(sw, handle, tmp_path):
             pairs = [tuple(map(int, ln.split(":"))) for ln in outs[dbname, "--topk"][qi]]
             assert pairs == list(zip(map(int, want_keys[qi][0]), map(int, want_keys[qi][1]))), (dbname, qi)
     assert outs["fasta", "--hits"] == outs["swdb", "--hits"] and outs["fasta", "--topk"] == outs["swdb", "--topk"]
+
+
+# ---- 8. the single forms are the batch forms of one query ---------------------------
+def raw(obj):
+    return bytes(memoryview(obj).cast("B"))
+
+
+@pytest.mark.parametrize("name", sorted(SCORINGS))
+def test_single_forms_equal_one_query_batches(sw, handle, name):
+    """sw_scan_hits_sig against sw_scan_batch_hits_sig and sw_scan_topk against
+    sw_scan_batch_topk at nq = 1, byte for byte: rows, sig, calib, nhits and
+    keys.  k is larger than the 130 subjects, so the slots past nhits (the
+    caller's bytes, here a pattern) and the keys' padding are compared too."""
+    capi = sw.capi
+    L = capi.lib()
+    mid, go, ge = SCORINGS[name]
+    subs, rids = layout_edges_subjects()
+    res, offs = pack(subs)
+    db = sw.Database(handle, res, offs, ids=rids)
+    q = np.random.default_rng(31).integers(0, 4, size=40).astype(np.uint8)
+    qp = q.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+    qoffs = np.array([0, len(q)], dtype=np.int64)
+    op = qoffs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    scoring = capi._ScoringArg(capi.builtin_matrix(mid), go, ge)
+    k = 200
+    got = {}
+    for form in ("single", "batch"):
+        hits, sigs, cal, nhits = (capi.Hit * k)(), (capi.Sig * k)(), capi.Calib(), ctypes.c_int32(-7)
+        keys = np.full(k, 0x5a5a5a5a5a5a5a5a, dtype=np.int64)
+        for buf in (hits, sigs, cal):
+            ctypes.memset(ctypes.addressof(buf), 0xa5, ctypes.sizeof(buf))
+        kp = keys.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        if form == "single":
+            rc = L.sw_scan_hits_sig(handle.ptr, db.ptr, qp, len(q), scoring.ptr(), k, hits, sigs, ctypes.byref(nhits),
+                                    ctypes.byref(cal))
+            rk = L.sw_scan_topk(handle.ptr, db.ptr, qp, len(q), scoring.ptr(), k, kp)
+        else:
+            rc = L.sw_scan_batch_hits_sig(handle.ptr, db.ptr, qp, op, 1, scoring.ptr(), k, hits, sigs,
+                                          ctypes.byref(nhits), ctypes.byref(cal))
+            rk = L.sw_scan_batch_topk(handle.ptr, db.ptr, qp, op, 1, scoring.ptr(), k, kp)
+        assert (rc, rk) == (0, 0), (form, L.sw_last_error())
+        got[form] = (raw(hits), raw(sigs), raw(cal), nhits.value, keys.tobytes())
+    assert got["single"][3] == 130
+    for what, a, b in zip(("rows", "sig", "calib", "nhits", "keys"), got["single"], got["batch"]):
+        assert a == b, what
+    rows = (capi.Hit * k).from_buffer_copy(got["single"][0])
+    assert any(rows[i].score > 0 for i in range(130)) and raw(rows)[130 * ctypes.sizeof(capi.Hit):] == \
+        b"\xa5" * (70 * ctypes.sizeof(capi.Hit))
+    keys = np.frombuffer(got["single"][4], dtype=np.int64)
+    assert np.all(keys[130:] == I64_MIN) and np.all(keys[:130] != I64_MIN)
+    db.close()

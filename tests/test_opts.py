@@ -54,19 +54,27 @@ def test_set_opts_argument_errors(sw):
 def test_no_environment_read_on_the_scan_path():
     """The library reads SW_* variables only in sw_opts_from_env (VERDICT r04
     item 8): the scan path's choices come from the handle's sw_opts."""
-    for src in ("sw_capi.cpp", "sw_kernels.hip", "sw_inter_x2.hip", "sw_intra_x2.hip", "sw_topk.hip",
-                "sw_profile.hip", "sw_synth.hip", "sw_align.hip", "sw_group.cpp", "sw_host.h", "sw_owned.h",
-                "sw_pack.cpp", "sw_pack.h", "sw_parallel.h", "sw_dbfile.cpp", "sw_dbfile.h",
-                "sw_synth_host.cpp", "sw_synth_host.h", "sw_synth_hash.h"):
+    # every source in the directory but the programs that link the library (the
+    # Makefile's HOSTOBJS: the CLI and the C++ drop-in pick their devices from
+    # SW_DEVICE & co.)
+    programs = re.search(r"^HOSTOBJS\s*:=\s*(.+)$", open(os.path.join(CSRC, "Makefile")).read(), re.M).group(1).split()
+    assert sorted(programs) == ["main", "sw_tests", "swsolver"]
+    sources = sorted(s for s in os.listdir(CSRC)
+                     if s.endswith((".cpp", ".hip", ".h")) and s.rsplit(".", 1)[0] not in programs)
+    assert len(sources) >= 30 and "sw_hits.hip" in sources and "sw_plan.cpp" in sources
+    defined_in = []
+    for src in sources:
         text = open(os.path.join(CSRC, src)).read()
         calls = [m.start() for m in re.finditer(r"\bgetenv\(", text)]
-        if src != "sw_capi.cpp":
+        if "int sw_opts_from_env(" not in text:
             assert not calls, src
             continue
+        defined_in.append(src)
         body = text[text.index("int sw_opts_from_env("):]
         body = body[:body.index("\n}\n")]
         start = text.index(body)
         assert calls and all(start <= c < start + len(body) for c in calls), "getenv outside sw_opts_from_env"
+    assert len(defined_in) == 1, defined_in
 
 
 def test_hip_resources_are_created_and_released_in_sw_host_h():
