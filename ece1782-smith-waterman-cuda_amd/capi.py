@@ -37,6 +37,8 @@ EXPORTED = (
     "sw_scan_pssm_topk", "sw_align_pssm",
     "sw_score_hist_device", "sw_score_hist", "sw_calib_fit", "sw_calib_sig",
     "sw_scan_hits_sig", "sw_scan_batch_hits_sig", "sw_scan_pssm_topk_calib",
+    "sw_sig_rank_table", "sw_sig_rank_min", "sw_sig_topk_device",
+    "sw_scan_hits_ranked", "sw_scan_batch_hits_ranked", "sw_scan_pssm_topk_ranked",
     "sw_db_save", "sw_db_load", "sw_db_subjects", "sw_db_create_synthetic", "sw_synth_tables",
     "sw_synth_lengths", "sw_group_create", "sw_group_destroy", "sw_group_info", "sw_group_handle",
     "sw_group_db_create", "sw_group_db_free", "sw_group_db_shard", "sw_group_scan", "sw_group_topk",
@@ -85,6 +87,11 @@ CALIB_SBINS = 512
 CALIB_CLIPPED = 1
 CALIB_FEW = 2
 CALIB_DEGENERATE = 4
+# Ranking by E-value (include/sw_amd.h SW_RANK_*): the rank value's scale, its
+# floor (a subject of score <= 0 or length 0) and the r_min nothing passes.
+RANK_SCALE = 4096
+RANK_FLOOR = -2 ** 32 + 1
+RANK_NONE = 2 ** 32
 
 
 class Calib(ctypes.Structure):
@@ -177,6 +184,14 @@ def lib():
     u8p = ctypes.POINTER(ctypes.c_uint8)
     i32p = ctypes.POINTER(ctypes.c_int32)
     i64p = ctypes.POINTER(ctypes.c_int64)
+
+    class f64(ctypes.c_double):
+        """A double argument for which None is 0.0, as it is 0 for every
+        pointer: a call of all-null arguments reaches the library's checks."""
+        @classmethod
+        def from_param(cls, v):
+            return ctypes.c_double(0.0 if v is None else v)
+
     sig = {
         "sw_version": (i32, []),
         "sw_build_id": (ctypes.c_char_p, []),
@@ -231,6 +246,17 @@ def lib():
                                                   ctypes.POINTER(Hit), ctypes.POINTER(Sig), i32p,
                                                   ctypes.POINTER(Calib)]),
         "sw_scan_pssm_topk_calib": (ctypes.c_int, [vp, vp, vp, i32, i32, i32, i64p, ctypes.POINTER(Calib)]),
+        "sw_sig_rank_table": (ctypes.c_int, [ctypes.POINTER(Calib), i32, i32p]),
+        "sw_sig_rank_min": (ctypes.c_int, [ctypes.POINTER(Calib), ctypes.c_double, i64p]),
+        "sw_sig_topk_device": (ctypes.c_int, [vp, vp, vp, i32p, i32, i64, i32, vp, vp]),
+        "sw_scan_hits_ranked": (ctypes.c_int, [vp, vp, u8p, i32, ctypes.POINTER(Scoring), i32, f64,
+                                               ctypes.POINTER(Hit), ctypes.POINTER(Sig), i32p, i64p,
+                                               ctypes.POINTER(Calib)]),
+        "sw_scan_batch_hits_ranked": (ctypes.c_int, [vp, vp, u8p, i64p, i32, ctypes.POINTER(Scoring), i32,
+                                                     f64, i64, ctypes.POINTER(Hit), ctypes.POINTER(Sig),
+                                                     i32p, i64p, ctypes.POINTER(Calib)]),
+        "sw_scan_pssm_topk_ranked": (ctypes.c_int, [vp, vp, vp, i32, i32, i32, f64, i32p, i32p,
+                                                    ctypes.POINTER(Sig), i32p, i64p, ctypes.POINTER(Calib)]),
         "sw_pssm_create": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int8), i32, ctypes.POINTER(vp)]),
         "sw_pssm_free": (ctypes.c_int, [vp]),
         "sw_pssm_length": (ctypes.c_int, [vp, i32p]),
@@ -720,6 +746,84 @@ class Database:
                                              out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(cal)))
         return out, cal
 
+    @staticmethod
+    def _max_evalue(max_evalue):
+        return float("inf") if max_evalue is None else float(max_evalue)
+
+    def scan_hits_ranked(self, query_codes, k, max_evalue=None, matrix=None, gap=2, gap_extend=None):
+        """scan_hits_sig ranked by E-value instead of raw score, with an
+        optional E-value cutoff (sw_scan_hits_ranked; max_evalue None: no
+        cutoff).  Returns (rows, Calib, n_pass): min(k, n_pass) rows in E-value
+        order; n_pass, the subjects that pass the cutoff, may exceed k."""
+        q, qp = _u8(query_codes)
+        sc = _ScoringArg(matrix, gap, gap if gap_extend is None else gap_extend)
+        out = (Hit * max(int(k), 1))()
+        sig = (Sig * max(int(k), 1))()
+        cal = Calib()
+        nhits, npass = ctypes.c_int32(0), ctypes.c_int64(0)
+        _check(lib().sw_scan_hits_ranked(self.handle.ptr, self._d, qp, len(q), sc.ptr(), k,
+                                         self._max_evalue(max_evalue), out, sig, ctypes.byref(nhits),
+                                         ctypes.byref(npass), ctypes.byref(cal)))
+        return [dict(out[i].as_dict(), **sig[i].as_dict()) for i in range(nhits.value)], cal, npass.value
+
+    def scan_batch_hits_ranked(self, queries, k, max_evalue=None, matrix=None, gap=2, gap_extend=None,
+                               score_bytes=0):
+        """scan_hits_ranked for every query of a batch (sw_scan_batch_hits_ranked;
+        score_bytes: the device memory the batch's score rows may take, 0 =
+        256 MiB).  Returns (rows, calibs, n_pass), each of len(queries)."""
+        cat, offs = self._cat(queries)
+        c, cp = _u8(cat)
+        sc = _ScoringArg(matrix, gap, gap if gap_extend is None else gap_extend)
+        nq, kk = len(queries), max(int(k), 1)
+        out = (Hit * max(nq * kk, 1))()
+        sig = (Sig * max(nq * kk, 1))()
+        cal = (Calib * max(nq, 1))()
+        nhits = np.zeros(max(nq, 1), dtype=np.int32)
+        npass = np.zeros(max(nq, 1), dtype=np.int64)
+        _check(lib().sw_scan_batch_hits_ranked(self.handle.ptr, self._d, cp,
+                                               offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nq, sc.ptr(), k,
+                                               self._max_evalue(max_evalue), int(score_bytes), out, sig,
+                                               nhits.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                               npass.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), cal))
+        rows = [[dict(out[q * kk + i].as_dict(), **sig[q * kk + i].as_dict()) for i in range(int(nhits[q]))]
+                for q in range(nq)]
+        return rows, [cal[q].copy() for q in range(nq)], [int(npass[q]) for q in range(nq)]
+
+    def scan_pssm_topk_ranked(self, pssm, k, max_evalue=None, gap_open=2, gap_extend=None):
+        """A PSSM scan ranked by E-value (sw_scan_pssm_topk_ranked): (rows,
+        Calib, n_pass), rows = dicts of id, score, evalue, bits, z."""
+        kk = max(int(k), 1)
+        ids = np.zeros(kk, dtype=np.int32)
+        scores = np.zeros(kk, dtype=np.int32)
+        sig = (Sig * kk)()
+        cal = Calib()
+        nhits, npass = ctypes.c_int32(0), ctypes.c_int64(0)
+        _check(lib().sw_scan_pssm_topk_ranked(self.handle.ptr, self._d, pssm.ptr, gap_open,
+                                              gap_open if gap_extend is None else gap_extend, k,
+                                              self._max_evalue(max_evalue),
+                                              ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                              scores.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), sig,
+                                              ctypes.byref(nhits), ctypes.byref(npass), ctypes.byref(cal)))
+        rows = [dict(id=int(ids[i]), score=int(scores[i]), **sig[i].as_dict()) for i in range(nhits.value)]
+        return rows, cal, npass.value
+
+    def sig_topk(self, scores_dev_ptr, adj, r_min, k):
+        """The k best subjects of a device score array (n_out int32) by rank
+        value under the adjustment table adj (int32 [max_len + 1]) with the
+        cutoff r_min (sw_sig_topk_device, then a synchronisation): (keys int64
+        [k], count of subjects with r >= r_min)."""
+        import torch
+        a = np.ascontiguousarray(adj, dtype=np.int32)
+        dev = torch.device("cuda", self.handle.device)
+        keys = torch.zeros(max(int(k), 1), dtype=torch.int64, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # the fills ran on torch's stream
+        _check(lib().sw_sig_topk_device(self.handle.ptr, self._d, ctypes.c_void_p(scores_dev_ptr),
+                                        a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(a) - 1, int(r_min), k,
+                                        ctypes.c_void_p(keys.data_ptr()), ctypes.c_void_p(count.data_ptr())))
+        torch.cuda.synchronize(dev)
+        return keys.cpu().numpy()[:k], int(count.cpu().numpy().view(np.uint32)[0])
+
     def scan_pssm(self, pssm, gap_open=2, gap_extend=None):
         """Synchronous scan of a Pssm; int32 scores indexed by id (sw_scan_pssm)."""
         out = np.zeros(self.n_out, dtype=np.int32)
@@ -864,6 +968,23 @@ def calib_sig(calib, score, slen):
     s = Sig()
     _check(lib().sw_calib_sig(ctypes.byref(calib), int(score), int(slen), ctypes.byref(s)))
     return s.evalue, s.bits, s.z
+
+
+def sig_rank_table(calib, max_len):
+    """adj[0 .. max_len] of a Calib (sw_sig_rank_table; host only): int32,
+    llround(4096 c ln L), zeros when the calibration is degenerate."""
+    adj = np.zeros(int(max_len) + 1, dtype=np.int32)
+    _check(lib().sw_sig_rank_table(ctypes.byref(calib), int(max_len), adj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    return adj
+
+
+def sig_rank_min(calib, max_evalue):
+    """The smallest rank value whose E-value is at most max_evalue under a
+    Calib (sw_sig_rank_min; host only); None or inf: RANK_FLOOR."""
+    r = ctypes.c_int64(0)
+    _check(lib().sw_sig_rank_min(ctypes.byref(calib), float("inf") if max_evalue is None else float(max_evalue),
+                                 ctypes.byref(r)))
+    return r.value
 
 
 class Group:

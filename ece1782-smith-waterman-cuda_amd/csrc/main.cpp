@@ -39,6 +39,14 @@
 // A calibration that clipped or is degenerate also warns on stderr: the
 // scoring has no local-alignment statistic, or the database is too uniform,
 // and the two columns mean nothing.  Without --evalue the output is unchanged.
+// Ranking by E-value: --rank evalue, valid only with --hits K --evalue (with
+// --query or --queries), prints the K most significant subjects in E-value
+// order (sw_scan_hits_ranked, sw_amd.h) instead of the K best raw scores;
+// --max-evalue X (X > 0), valid only with --rank evalue, keeps only subjects
+// with E <= X.  Both are checked before any file is read.  The rows are the
+// same 14 columns, and one more line follows a query's calibration line:
+//   # significant <subjects that pass the cutoff> shown <rows>
+// Without the two flags the output is unchanged.
 // Batches of queries: --queries FILE takes the place of --query: a FASTA file
 // of several records (sw_solver_read_queries), searched in one call of the
 // library (sw_scan_batch_hits / sw_scan_batch_topk) against a FASTA or a
@@ -51,6 +59,7 @@
 #include <sys/time.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -90,7 +99,10 @@ void usage() {
               << "  --hits arg            Print the arg best subjects (1..4096) as a hit table: id score q_begin\n"
               << "                        q_end s_begin s_end s_len length identities positives gap_opens gaps\n"
               << "  --evalue              With --hits: append evalue and bits to each row (calibrated on the\n"
-              << "                        scan's own scores) and print a '# calibration' line per query\n";
+              << "                        scan's own scores) and print a '# calibration' line per query\n"
+              << "  --rank arg            evalue: with --hits K --evalue, rank by E-value instead of raw score and\n"
+              << "                        print a '# significant N shown M' line per query\n"
+              << "  --max-evalue arg      With --rank evalue: only subjects with an E-value of at most arg (> 0)\n";
 }
 
 // a whole-string integer in [lo, hi]
@@ -124,7 +136,7 @@ int main(int argc, char* argv[]) {
         }
         if (key != "query" && key != "db" && key != "metrics-json" && key != "make-db" && key != "gpus" &&
             key != "matrix" && key != "gap-open" && key != "gap-extend" && key != "topk" && key != "pssm" && key != "hits" &&
-            key != "queries" && key != "evalue") {
+            key != "queries" && key != "evalue" && key != "rank" && key != "max-evalue") {
             std::cerr << "unrecognised option '--" << key << "'\n";
             return 1;
         }
@@ -134,6 +146,30 @@ int main(int argc, char* argv[]) {
     if (evalue && !opt.count("hits") && !help) {  // checked before any file is read
         std::cerr << "--evalue needs --hits K: it adds columns to the hit table\n";
         return 1;
+    }
+    const bool ranked = opt.count("rank") != 0;
+    double max_evalue = HUGE_VAL;  // no cutoff
+    if (ranked && !help) {  // checked before any file is read
+        if (opt["rank"] != "evalue") {
+            std::cerr << "--rank takes one value: evalue\n";
+            return 1;
+        }
+        if (!evalue || !opt.count("hits")) {
+            std::cerr << "--rank evalue needs --hits K --evalue: it orders the hit table by its evalue column\n";
+            return 1;
+        }
+    }
+    if (opt.count("max-evalue") && !help) {
+        if (!ranked) {
+            std::cerr << "--max-evalue needs --rank evalue: the cutoff is applied by the ranking\n";
+            return 1;
+        }
+        char* end = nullptr;
+        max_evalue = std::strtod(opt["max-evalue"].c_str(), &end);
+        if (opt["max-evalue"].empty() || *end != '\0' || !(max_evalue > 0)) {
+            std::cerr << "--max-evalue must be a number > 0\n";
+            return 1;
+        }
     }
     const bool use_queries = opt.count("queries") != 0;
     if (use_queries && !help) {  // checked before any file is read
@@ -267,6 +303,7 @@ int main(int argc, char* argv[]) {
     std::vector<sw_sig> sigs;  // --evalue: beside rows / brows
     std::vector<std::vector<sw_sig> > bsigs;
     std::vector<sw_calib> calibs;  // ... one per query
+    std::vector<int64_t> npass;    // --rank evalue: per query, the subjects that pass the cutoff
     int64_t num_subjects = 0, length_sum = 0;
     double solve_s = 0, parse_s = 0;
     if (!binary) {
@@ -275,7 +312,14 @@ int main(int argc, char* argv[]) {
         parse_s = now_s() - t_parse;
         const double t_solve = now_s();
         try {
-            if (use_queries && hits && evalue) brows = smith_waterman_cuda_batch_hits_sig(qseqs, db, hits, &bsigs, &calibs);
+            if (use_queries && ranked)
+                brows = smith_waterman_cuda_batch_hits_ranked(qseqs, db, hits, max_evalue, &bsigs, &npass, &calibs);
+            else if (ranked) {
+                calibs.resize(1);
+                npass.resize(1);
+                rows = smith_waterman_cuda_hits_ranked(query, db, hits, max_evalue, &sigs, &npass[0], &calibs[0]);
+            }
+            else if (use_queries && hits && evalue) brows = smith_waterman_cuda_batch_hits_sig(qseqs, db, hits, &bsigs, &calibs);
             else if (hits && evalue) {
                 calibs.resize(1);
                 rows = smith_waterman_cuda_hits_sig(query, db, hits, &sigs, &calibs[0]);
@@ -335,11 +379,18 @@ int main(int argc, char* argv[]) {
                 int32_t nhits = 0;
                 std::vector<sw_sig> allsig(evalue ? all.size() : 0);
                 calibs.resize(evalue ? qseqs.size() : 0);
-                if (evalue ? sw_scan_batch_hits_sig(h, sdb, cat.data(), qoffs.data(), nq, &sc, hits, all.data(),
+                std::vector<int32_t> qhits(qseqs.size(), 0);  // --rank evalue: a query's row count is its own
+                npass.resize(ranked ? qseqs.size() : 0);
+                if (ranked) {
+                    if (sw_scan_batch_hits_ranked(h, sdb, cat.data(), qoffs.data(), nq, &sc, hits, max_evalue, 0, all.data(),
+                                                  allsig.data(), qhits.data(), npass.data(), calibs.data()))
+                        return die("sw_scan_batch_hits_ranked");
+                } else if (evalue ? sw_scan_batch_hits_sig(h, sdb, cat.data(), qoffs.data(), nq, &sc, hits, all.data(),
                                                     allsig.data(), &nhits, calibs.data())
                            : sw_scan_batch_hits(h, sdb, cat.data(), qoffs.data(), nq, &sc, hits, all.data(), &nhits))
                     return die("sw_scan_batch_hits");
                 for (size_t i = 0; i < qseqs.size(); ++i) {
+                    if (ranked) nhits = qhits[i];
                     brows.push_back(std::vector<sw_hit>(all.begin() + static_cast<int64_t>(i) * hits,
                                                         all.begin() + static_cast<int64_t>(i) * hits + nhits));
                     if (evalue)
@@ -364,7 +415,12 @@ int main(int argc, char* argv[]) {
             int32_t nhits = 0;
             sigs.resize(evalue ? rows.size() : 0);
             calibs.resize(evalue ? 1 : 0);
-            if (evalue ? sw_scan_hits_sig(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, hits, rows.data(),
+            npass.resize(ranked ? 1 : 0);
+            if (ranked) {
+                if (sw_scan_hits_ranked(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, hits, max_evalue,
+                                        rows.data(), sigs.data(), &nhits, npass.data(), calibs.data()))
+                    return die("sw_scan_hits_ranked");
+            } else if (evalue ? sw_scan_hits_sig(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, hits, rows.data(),
                                           sigs.data(), &nhits, calibs.data())
                        : sw_scan_hits(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, hits, rows.data(), &nhits))
                 return die("sw_scan_hits");
@@ -448,13 +504,19 @@ int main(int argc, char* argv[]) {
                       << ": the calibration is degenerate (too few or too uniform scores): every evalue is the"
                          " database's size\n";
     };
+    // --rank evalue: how many subjects passed the cutoff, and how many of them are shown
+    auto print_significant = [&](size_t i, size_t shown) {
+        if (i < npass.size()) cout << "# significant " << npass[i] << " shown " << shown << "\n";
+    };
     print_scores(result);
     if (evalue && !use_queries && !calibs.empty()) print_calib(calibs[0], 0);
+    if (!use_queries) print_significant(0, rows.size());
     print_rows(rows, evalue && !use_queries ? &sigs : nullptr);
     // --queries: a block per query, in file order (index from 0; "-" for a header without a name)
     for (size_t i = 0; i < qseqs.size(); ++i) {
         cout << "# query " << i << " " << (qnames[i].empty() ? "-" : qnames[i]) << " " << qseqs[i].size() << "\n";
         if (evalue && i < calibs.size()) print_calib(calibs[i], i);
+        if (i < brows.size()) print_significant(i, brows[i].size());
         if (i < brows.size()) print_rows(brows[i], evalue && i < bsigs.size() ? &bsigs[i] : nullptr);
         if (i < bresult.size()) print_scores(bresult[i]);
     }

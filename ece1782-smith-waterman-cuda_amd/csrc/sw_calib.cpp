@@ -124,4 +124,41 @@ void significance(const sw_calib& c, int32_t score, int32_t slen, sw_sig* out) {
     out->bits = (t + std::log(static_cast<double>(c.qlen) * static_cast<double>(slen))) / kLn2;
 }
 
+static bool degenerate(const sw_calib& c) { return (c.status & SW_CALIB_DEGENERATE) || !(c.sigma > 0); }
+
+void rank_table(const sw_calib& c, int32_t max_len, int32_t* adj) {
+    const bool flat = degenerate(c);
+    adj[0] = 0;
+    for (int32_t L = 1; L <= max_len; ++L) {
+        if (flat) {
+            adj[L] = 0;
+            continue;
+        }
+        const double v = static_cast<double>(kRankScale) * c.c * std::log(static_cast<double>(L));
+        adj[L] = v >= 2147483647.0 ? INT32_MAX : v <= -2147483648.0 ? INT32_MIN : static_cast<int32_t>(std::llround(v));
+    }
+}
+
+bool rank_min(const sw_calib& c, double max_evalue, int64_t* r_min) {
+    if (!(max_evalue > 0)) return false;  // (NaN too)
+    const double n_db = static_cast<double>(c.n_db);
+    if (max_evalue >= n_db) {  // (+inf too)
+        *r_min = kRankFloor;
+        return true;
+    }
+    if (degenerate(c)) {  // every E-value is n_db
+        *r_min = kRankNone;
+        return true;
+    }
+    // E = n_db (1 - exp(-exp(-t))), t = (pi / sqrt 6) z + gamma, solved for z
+    const double t = -std::log(-std::log1p(-max_evalue / n_db));
+    const double z_min = (t - kEulerGamma) / kPiOverSqrt6;
+    const double v = std::ceil(static_cast<double>(kRankScale) * (c.a + c.sigma * z_min));
+    // (a real cutoff stays above the floor: a subject of score <= 0 has E = n_db)
+    *r_min = !(v > static_cast<double>(kRankFloor)) ? kRankFloor + 1
+             : v >= static_cast<double>(kRankNone)  ? kRankNone
+                                                    : static_cast<int64_t>(v);
+    return true;
+}
+
 }  // namespace swcalib

@@ -49,6 +49,34 @@ SW_CALIB_HD inline int score_bin(int32_t s) { return s < 0 ? 0 : s > kSBins - 1 
 void fit(const uint32_t* hist, int32_t qlen, sw_calib* out);
 void significance(const sw_calib& c, int32_t score, int32_t slen, sw_sig* out);
 
+// ---- ranking by E-value (include/sw_amd.h "ranking by E-value") --------------
+// The rank value and its key, integer only: the host, the device pass
+// (sw_sigkeys.hip) and the tests' restatement agree bit for bit.
+constexpr int64_t kRankScale = SW_RANK_SCALE;
+constexpr int64_t kRankFloor = SW_RANK_FLOOR;
+constexpr int64_t kRankNone = SW_RANK_NONE;
+constexpr int64_t kRankCeil = kRankNone - 1;       // 2^32 - 1
+constexpr int32_t kRankMaxScore = (1 << 20) - 1;
+
+// r(s, L) given adj = adj[min(L, max_len)].
+SW_CALIB_HD inline int64_t rank_value(int32_t s, int32_t L, int32_t adj) {
+    if (s <= 0 || L <= 0) return kRankFloor;
+    const int64_t r = static_cast<int64_t>(s > kRankMaxScore ? kRankMaxScore : s) * kRankScale - adj;
+    return r < kRankFloor ? kRankFloor : r > kRankCeil ? kRankCeil : r;
+}
+// r descending, then id ascending (0 <= id < 2^31); always above INT64_MIN.
+SW_CALIB_HD inline int64_t rank_key(int64_t r, int32_t id) {
+    return r * (int64_t{1} << 31) + ((int64_t{1} << 31) - 1 - id);
+}
+SW_CALIB_HD inline int32_t rank_key_id(int64_t key) {
+    return static_cast<int32_t>((int64_t{1} << 31) - 1 - (key & ((int64_t{1} << 31) - 1)));
+}
+
+// sw_sig_rank_table / sw_sig_rank_min (argument checks are the caller's but
+// max_evalue's: false for max_evalue <= 0 or NaN).
+void rank_table(const sw_calib& c, int32_t max_len, int32_t* adj);
+bool rank_min(const sw_calib& c, double max_evalue, int64_t* r_min);
+
 }  // namespace swcalib
 
 #endif  // SW_CALIB_H

@@ -522,4 +522,17 @@ hipError_t launch_topk(const TopkSrc& src, int64_t n, int k, int64_t* out, int64
 hipError_t launch_score_hist(const int32_t* scores, const int32_t* rid, const int32_t* slen, int64_t n,
                              uint32_t* hist, hipStream_t s);
 
+// Ranking by E-value (sw_sigkeys.hip; the rank value and key are sw_calib.h's):
+// subject g of [0, n), of result id r = rid ? rid[g] : g, writes keys[g] =
+// rank_key(rank_value(scores[r], slen[g], adj[min(slen[g], max_len)]), r), or
+// INT64_MIN below r_min, and the subjects at or above r_min are counted into
+// *count (device uint32, zeroed by the caller).
+hipError_t launch_sig_keys(const int32_t* scores, const int32_t* rid, const int32_t* slen, const int32_t* adj,
+                           int32_t max_len, int64_t r_min, int64_t n, int64_t* keys, uint32_t* count, hipStream_t s);
+// The rows {result id, score, subject length, 0} of the selected keys sel[0 .. k)
+// (launch_topk's output over keys[0 .. n): best first, INT64_MIN past the
+// last) into rows[4 p] for sel[p]; rows of absent keys are not written.
+hipError_t launch_sig_gather(const int32_t* scores, const int32_t* rid, const int32_t* slen, const int64_t* keys,
+                             int64_t n, const int64_t* sel, int32_t k, int32_t* rows, hipStream_t s);
+
 }  // namespace swk

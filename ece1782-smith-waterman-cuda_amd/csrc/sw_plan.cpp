@@ -657,6 +657,12 @@ std::vector<int64_t> align_groups(int32_t qlen, const int64_t* slens, int64_t n,
     return ends;
 }
 
+int32_t ranked_groups(int32_t nq, int64_t slots, int64_t score_bytes) {
+    const int64_t budget = score_bytes == 0 ? kRankedRowsBudget : score_bytes;
+    const int64_t rows = slots > 0 ? budget / (4 * slots) : nq;  // (no slots: rows cost nothing)
+    return static_cast<int32_t>(std::max<int64_t>(1, std::min<int64_t>(nq, rows)));
+}
+
 int64_t hits_cost(int32_t qlen, int64_t slen) {
     if (qlen <= 0 || slen <= 0) return 0;
     constexpr int64_t kWaveRows = swk::kLanes * swk::kHitsRowsPerLane;

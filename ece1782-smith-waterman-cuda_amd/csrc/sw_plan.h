@@ -202,4 +202,11 @@ constexpr int64_t kAlignDirsBudget = int64_t(1) << 30;
 // ends.back() == n; empty for n == 0.
 std::vector<int64_t> align_groups(int32_t qlen, const int64_t* slens, int64_t n, int64_t budget = kAlignDirsBudget);
 
+// Score rows a batch ranked by E-value keeps (sw_scan_batch_hits_ranked: a
+// query's fit precedes its ranking, so the queries of a group keep a row
+// each): G = max(1, min(nq, score_bytes / (4 slots))), slots = max_id + 1
+// int32 per row; score_bytes 0 = the default budget, a negative one = one row.
+constexpr int64_t kRankedRowsBudget = int64_t(256) << 20;
+int32_t ranked_groups(int32_t nq, int64_t slots, int64_t score_bytes);
+
 }  // namespace swplan

@@ -402,6 +402,164 @@ int scan_hits(sw_handle* h, const sw_db* db, const uint8_t* queries, const int64
     return check_fault(h);
 }
 
+// ---- ranking by E-value (include/sw_amd.h; sw_sigkeys.hip) ---------------------
+// sw_sig_topk_device's enqueue, on the handle's stream: the adjustment table
+// goes up, the count is zeroed, every subject's key is written into the
+// handle's workspace behind the top-K's own part, and the existing top-K
+// selects over those n keys.  rows (nullable, device [k][4]): the gather too.
+int sig_topk_enqueue(sw_handle* h, sw_db* db, const int32_t* scores_dev, const int32_t* adj_host, int32_t max_len,
+                     int64_t r_min, int32_t k, int64_t* keys_out_dev, uint32_t* count_out_dev, int32_t* rows_dev) {
+    const int64_t n = db->n;
+    const size_t tw = static_cast<size_t>(round_up(static_cast<int64_t>(swk::topk_workspace_bytes(n, k)), 8));
+    const size_t kbytes = static_cast<size_t>(n) * sizeof(int64_t);
+    const size_t abytes = (static_cast<size_t>(max_len) + 1) * sizeof(int32_t);
+    int rc;
+    if ((rc = ensure_topk_work(h, tw + kbytes + abytes))) return rc;
+    int64_t* const keys = h->d_topk_work.get() + tw / sizeof(int64_t);  // (aliases into the workspace)
+    int32_t* const adj = reinterpret_cast<int32_t*>(keys + n);
+    hipStream_t const s = h->stream.get();
+    HIPCHECK(hipMemcpyAsync(adj, adj_host, abytes, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(count_out_dev, 0, sizeof(uint32_t), s));
+    const int32_t *rid = nullptr, *slen = nullptr;
+    if (n > 0) {
+        if ((rc = subject_ids(db, &rid))) return rc;
+        if ((rc = subject_lengths(db, &slen))) return rc;
+    }
+    HIPCHECK(swk::launch_sig_keys(scores_dev, rid, slen, adj, max_len, r_min, n, keys, count_out_dev, s));
+    swk::TopkSrc src{};
+    src.keys = keys;
+    HIPCHECK(swk::launch_topk(src, n, k, keys_out_dev, h->d_topk_work.get(), s));
+    h->launches += 2;
+    if (rows_dev) {
+        HIPCHECK(swk::launch_sig_gather(scores_dev, rid, slen, keys, n, keys_out_dev, k, rows_dev, s));
+        ++h->launches;
+    }
+    return SW_OK;
+}
+
+// What the ranked forms bring down: per query k keys, the count of subjects
+// that passed, the calibration, and (PSSM form) k gathered rows of 4 ints.
+struct Ranked {
+    std::vector<int64_t> keys;
+    std::vector<uint32_t> count;
+    std::vector<sw_calib> calib;
+    std::vector<int32_t> rows;
+};
+
+// The scans of srcs[0 .. nq) ranked by E-value.  A query's fit precedes its
+// ranking, so the batch keeps G score rows (swplan::ranked_groups) and runs
+// groups of G queries: the scans and their tables, one synchronisation, the
+// fits, then the G key passes and selections in stream order; one more
+// synchronisation brings every query's keys and count down.
+int ranked_keys(sw_handle* h, const sw_db* cdb, const QuerySrc* srcs, int32_t nq, int32_t k, double max_evalue,
+                int64_t score_bytes, bool gather, Ranked& o) {
+    sw_db* db = mutable_db(cdb);
+    const size_t nkeys = static_cast<size_t>(nq) * static_cast<size_t>(k);
+    o.keys.assign(nkeys, INT64_MIN);
+    o.count.assign(static_cast<size_t>(nq), 0);
+    o.calib.assign(static_cast<size_t>(nq), sw_calib{});
+    o.rows.assign(gather ? nkeys * 4 : 0, 0);
+    if (nq == 0) return SW_OK;
+    if (db->n == 0) {  // the calibration of an empty table
+        const std::vector<uint32_t> zero(swcalib::kCells, 0);
+        for (int32_t q = 0; q < nq; ++q) calib_of(db, zero.data(), srcs[q].qlen, &o.calib[q]);
+        return SW_OK;
+    }
+    if (db->h != h) return fail(SW_E_INVALID, "the database belongs to another handle");
+    int rc;
+    HIPCHECK(hipSetDevice(h->device));
+    const int64_t slots = static_cast<int64_t>(db->max_id) + 1, rs = round_up(slots, 2);
+    const int32_t G = swplan::ranked_groups(nq, slots, score_bytes);
+    // the G score rows, then the keys, the counts, the G tables, the gathered rows
+    const size_t ncnt = static_cast<size_t>(round_up(nq, 2));
+    const size_t ntab = static_cast<size_t>(G) * swcalib::kCells;
+    if ((rc = ensure_scores(h, static_cast<size_t>(G) * rs + 2 * nkeys + ncnt + ntab + o.rows.size()))) return rc;
+    int64_t* const keys_dev = reinterpret_cast<int64_t*>(h->d_scores.get() + static_cast<size_t>(G) * rs);
+    uint32_t* const cnt_dev = reinterpret_cast<uint32_t*>(keys_dev + nkeys);
+    uint32_t* const hist_dev = cnt_dev + ncnt;
+    int32_t* const rows_dev = gather ? reinterpret_cast<int32_t*>(hist_dev + ntab) : nullptr;
+    uint32_t* hist = nullptr;  // (pinned)
+    if ((rc = ensure_hist_host(h, static_cast<size_t>(G), &hist))) return rc;
+    hipStream_t const s = h->stream.get();
+    // every query's adjustment table stays alive until the last synchronisation (its upload's source)
+    std::vector<std::vector<int32_t>> adj(static_cast<size_t>(nq));
+    for (int32_t g0 = 0; g0 < nq; g0 += G) {
+        const int32_t m = std::min(G, nq - g0);
+        for (int32_t j = 0; j < m; ++j)
+            if ((rc = scan_impl(h, db, srcs[g0 + j], h->d_scores.get() + static_cast<size_t>(j) * rs, false, nullptr,
+                                hist_dev + static_cast<size_t>(j) * swcalib::kCells)))
+                return rc;
+        HIPCHECK(hipMemcpyAsync(hist, hist_dev, static_cast<size_t>(m) * swcalib::kCells * sizeof(uint32_t),
+                                hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipStreamSynchronize(s));
+        if ((rc = check_fault(h))) return rc;
+        for (int32_t j = 0; j < m; ++j) {
+            const int32_t q = g0 + j;
+            calib_of(db, hist + static_cast<size_t>(j) * swcalib::kCells, srcs[q].qlen, &o.calib[q]);
+            int64_t r_min = 0;
+            if (!swcalib::rank_min(o.calib[q], max_evalue, &r_min)) return fail(SW_E_INVALID, "max_evalue must be > 0");
+            adj[q].resize(static_cast<size_t>(db->max_len) + 1);
+            swcalib::rank_table(o.calib[q], db->max_len, adj[q].data());
+            if ((rc = sig_topk_enqueue(h, db, h->d_scores.get() + static_cast<size_t>(j) * rs, adj[q].data(), db->max_len,
+                                       r_min, k, keys_dev + static_cast<size_t>(q) * k, cnt_dev + q,
+                                       rows_dev ? rows_dev + static_cast<size_t>(q) * k * 4 : nullptr)))
+                return rc;
+        }
+    }
+    HIPCHECK(hipMemcpyAsync(o.keys.data(), keys_dev, nkeys * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(o.count.data(), cnt_dev, static_cast<size_t>(nq) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (gather) HIPCHECK(hipMemcpyAsync(o.rows.data(), rows_dev, o.rows.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    return check_fault(h);
+}
+
+// sw_scan_hits_ranked and its batch form: ranked_keys, then the hit-table
+// rows of every query's min(k, n_pass) selected ids in one launch sequence.
+int scan_hits_ranked(sw_handle* h, const sw_db* db, const uint8_t* queries, const int64_t* qoffsets, int32_t nq,
+                     const sw_scoring* sc, int32_t k, double max_evalue, int64_t score_bytes, sw_hit* out, sw_sig* sig,
+                     int32_t* nhits, int64_t* n_pass, sw_calib* calib) {
+    Ranked r;
+    int rc;
+    if ((rc = ranked_keys(h, db, batch_srcs(queries, qoffsets, nq, sc).data(), nq, k, max_evalue, score_bytes, false, r)))
+        return rc;
+    std::vector<int32_t> qidx, ids;
+    std::vector<size_t> first(static_cast<size_t>(nq) + 1, 0);
+    for (int32_t q = 0; q < nq; ++q) {
+        const int32_t m = static_cast<int32_t>(std::min<int64_t>(k, r.count[q]));
+        for (int32_t i = 0; i < m; ++i) {
+            qidx.push_back(q);
+            ids.push_back(swcalib::rank_key_id(r.keys[static_cast<size_t>(q) * k + i]));
+        }
+        first[q + 1] = ids.size();
+    }
+    std::vector<sw_hit> rows(ids.size());
+    if ((rc = hits_impl(h, db, queries, qoffsets, nq, sc, qidx.data(), ids.data(), static_cast<int64_t>(ids.size()),
+                        rows.data())))
+        return rc;
+    for (int32_t q = 0; q < nq; ++q) {
+        const size_t m = first[q + 1] - first[q];
+        for (size_t i = 0; i < m; ++i) {
+            const sw_hit& row = rows[first[q] + i];
+            out[static_cast<size_t>(q) * k + i] = row;
+            swcalib::significance(r.calib[q], row.score, row.s_len, &sig[static_cast<size_t>(q) * k + i]);
+        }
+        nhits[q] = static_cast<int32_t>(m);
+        n_pass[q] = r.count[q];
+        if (calib) calib[q] = r.calib[q];
+    }
+    return check_fault(h);
+}
+
+// What the ranked entry points check first (nhits and n_pass start at 0).
+int check_ranked_args(sw_handle* h, const sw_db* db, int32_t nq, int32_t k, double max_evalue, const void* out,
+                      const sw_sig* sig, int32_t* nhits, int64_t* n_pass) {
+    if (!h || !db || k <= 0 || k > 4096 || nq < 0 || (nq > 0 && (!nhits || !n_pass || !out || !sig)))
+        return fail(SW_E_INVALID, "bad argument (1 <= k <= 4096)");
+    if (!(max_evalue > 0)) return fail(SW_E_INVALID, "max_evalue must be > 0 (+inf: no cutoff)");
+    for (int32_t q = 0; q < nq; ++q) nhits[q] = 0, n_pass[q] = 0;
+    return SW_OK;
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -569,6 +727,59 @@ int sw_calib_sig(const sw_calib* calib, int32_t score, int32_t slen, sw_sig* out
     return SW_OK;
 }
 
+// ---- ranking by E-value -------------------------------------------------------
+static int check_calib(const sw_calib* calib) {
+    if (!calib) return fail(SW_E_INVALID, "null argument");
+    if (calib->size != static_cast<int32_t>(sizeof(sw_calib)))
+        return fail(SW_E_INVALID, "sw_calib.size is not this library's (use sw_calib_fit)");
+    return SW_OK;
+}
+
+int sw_sig_rank_table(const sw_calib* calib, int32_t max_len, int32_t* adj) {
+    if (int rc = check_calib(calib)) return rc;
+    if (!adj || max_len < 0) return fail(SW_E_INVALID, "null argument");
+    swcalib::rank_table(*calib, max_len, adj);
+    return SW_OK;
+}
+
+int sw_sig_rank_min(const sw_calib* calib, double max_evalue, int64_t* r_min) {
+    if (int rc = check_calib(calib)) return rc;
+    if (!r_min) return fail(SW_E_INVALID, "null argument");
+    if (!swcalib::rank_min(*calib, max_evalue, r_min)) return fail(SW_E_INVALID, "max_evalue must be > 0 (+inf: no cutoff)");
+    return SW_OK;
+}
+
+int sw_sig_topk_device(sw_handle* h, const sw_db* cdb, const int32_t* scores_dev, const int32_t* adj_host,
+                       int32_t max_len, int64_t r_min, int32_t k, int64_t* keys_out_dev, uint32_t* count_out_dev) {
+    sw_db* db = mutable_db(cdb);
+    if (!h || !db || !adj_host || max_len < 0 || !keys_out_dev || !count_out_dev || k <= 0 || k > 4096 ||
+        (db->n > 0 && !scores_dev))
+        return fail(SW_E_INVALID, "bad argument (1 <= k <= 4096)");
+    if (db->h != h) return fail(SW_E_INVALID, "the database belongs to another handle");
+    int rc;
+    if ((rc = check_fault(h))) return rc;
+    HIPCHECK(hipSetDevice(h->device));
+    if (!db->lay.built && (rc = build_db(db))) return rc;
+    return sig_topk_enqueue(h, db, scores_dev, adj_host, max_len, r_min, k, keys_out_dev, count_out_dev, nullptr);
+}
+
+int sw_scan_hits_ranked(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
+                        int32_t k, double max_evalue, sw_hit* out, sw_sig* sig, int32_t* nhits, int64_t* n_pass,
+                        sw_calib* calib) {
+    if (int rc = check_ranked_args(h, db, 1, k, max_evalue, out, sig, nhits, n_pass)) return rc;
+    const int64_t offs[2] = {0, qlen};
+    return scan_hits_ranked(h, db, query, offs, 1, sc, k, max_evalue, 0, out, sig, nhits, n_pass, calib);
+}
+
+int sw_scan_batch_hits_ranked(sw_handle* h, const sw_db* db, const uint8_t* queries, const int64_t* qoffsets, int32_t nq,
+                              const sw_scoring* sc, int32_t k, double max_evalue, int64_t score_bytes, sw_hit* out,
+                              sw_sig* sig, int32_t* nhits, int64_t* n_pass, sw_calib* calib) {
+    int rc;
+    if ((rc = check_ranked_args(h, db, nq, k, max_evalue, out, sig, nhits, n_pass))) return rc;
+    if ((rc = check_batch_args(h, db, queries, qoffsets, nq))) return rc;
+    return scan_hits_ranked(h, db, queries, qoffsets, nq, sc, k, max_evalue, score_bytes, out, sig, nhits, n_pass, calib);
+}
+
 // ---- position-specific scoring matrices ----------------------------------
 int sw_pssm_create(sw_handle* h, const int8_t* rows, int32_t qlen, sw_pssm** out) {
     if (!h || !out || qlen < 0 || (qlen > 0 && !rows)) return fail(SW_E_INVALID, "null argument");
@@ -636,6 +847,28 @@ int sw_scan_pssm_topk_calib(sw_handle* h, const sw_db* db, const sw_pssm* p, int
     const QuerySrc src = pssm_src(p, gap_open, gap_extend);
     if (int rc = scan_topk_host(h, db, &src, 1, k, keys_host, hist)) return rc;
     calib_of(db, hist, p->qlen, calib);
+    return SW_OK;
+}
+
+int sw_scan_pssm_topk_ranked(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open, int32_t gap_extend,
+                             int32_t k, double max_evalue, int32_t* ids, int32_t* scores, sw_sig* sig, int32_t* nhits,
+                             int64_t* n_pass, sw_calib* calib) {
+    if (!scores) return fail(SW_E_INVALID, "null argument");
+    int rc;
+    if ((rc = check_pssm(h, p, gap_open, gap_extend))) return rc;
+    if ((rc = check_ranked_args(h, db, 1, k, max_evalue, ids, sig, nhits, n_pass))) return rc;
+    const QuerySrc src = pssm_src(p, gap_open, gap_extend);
+    Ranked r;
+    if ((rc = ranked_keys(h, db, &src, 1, k, max_evalue, 0, true, r))) return rc;
+    const int32_t m = static_cast<int32_t>(std::min<int64_t>(k, r.count[0]));
+    for (int32_t i = 0; i < m; ++i) {  // the gathered rows: {id, score, subject length, 0}
+        ids[i] = r.rows[4 * i];
+        scores[i] = r.rows[4 * i + 1];
+        swcalib::significance(r.calib[0], r.rows[4 * i + 1], r.rows[4 * i + 2], &sig[i]);
+    }
+    *nhits = m;
+    *n_pass = r.count[0];
+    if (calib) *calib = r.calib[0];
     return SW_OK;
 }
 

@@ -549,8 +549,10 @@ std::vector<seqid_score> smith_waterman_cuda_topk(FASTAQuery& query, FASTADataba
 }
 
 namespace {
-// smith_waterman_cuda_hits; sig (nullable): its _sig form (sw_scan_hits_sig).
-std::vector<sw_hit> hits_call(FASTAQuery& query, FASTADatabase& db, int k, std::vector<sw_sig>* sig, sw_calib* calib) {
+// smith_waterman_cuda_hits; sig (nullable): its _sig form (sw_scan_hits_sig);
+// n_pass (nullable, with sig): its _ranked form under max_evalue (sw_scan_hits_ranked).
+std::vector<sw_hit> hits_call(FASTAQuery& query, FASTADatabase& db, int k, std::vector<sw_sig>* sig, sw_calib* calib,
+                              int64_t* n_pass = nullptr, double max_evalue = 0) {
     if (k < 1 || k > 4096) throw std::invalid_argument("the hit table needs 1 <= k <= 4096");
     std::lock_guard<std::mutex> lock(g_mu);
     // coordinates are those of the sequences as written: no '/' padding of
@@ -575,12 +577,14 @@ std::vector<sw_hit> hits_call(FASTAQuery& query, FASTADatabase& db, int k, std::
     t0 = now_s();
     int32_t nhits = 0;
     if (sig) sig->assign(static_cast<size_t>(k), sw_sig{});
-    const int rc = sig ? sw_scan_hits_sig(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, k, out.data(),
-                                          sig->data(), &nhits, calib)
-                       : sw_scan_hits(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, k, out.data(), &nhits);
+    const int rc = n_pass ? sw_scan_hits_ranked(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, k, max_evalue,
+                                                out.data(), sig->data(), &nhits, n_pass, calib)
+                   : sig  ? sw_scan_hits_sig(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, k, out.data(),
+                                             sig->data(), &nhits, calib)
+                          : sw_scan_hits(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, k, out.data(), &nhits);
     g_timing.scan_s = now_s() - t0;
     sw_db_free(sdb);
-    check(rc, sig ? "sw_scan_hits_sig" : "sw_scan_hits");
+    check(rc, n_pass ? "sw_scan_hits_ranked" : sig ? "sw_scan_hits_sig" : "sw_scan_hits");
     out.resize(static_cast<size_t>(nhits));
     if (sig) sig->resize(static_cast<size_t>(nhits));
     return out;
@@ -595,6 +599,13 @@ std::vector<sw_hit> smith_waterman_cuda_hits_sig(FASTAQuery& query, FASTADatabas
                                                  sw_calib* calib) {
     if (!sig) throw std::invalid_argument("smith_waterman_cuda_hits_sig needs a vector for the significances");
     return hits_call(query, db, k, sig, calib);
+}
+
+std::vector<sw_hit> smith_waterman_cuda_hits_ranked(FASTAQuery& query, FASTADatabase& db, int k, double max_evalue,
+                                                    std::vector<sw_sig>* sig, int64_t* n_pass, sw_calib* calib) {
+    if (!sig) throw std::invalid_argument("smith_waterman_cuda_hits_ranked needs a vector for the significances");
+    int64_t np = 0;
+    return hits_call(query, db, k, sig, calib, n_pass ? n_pass : &np, max_evalue);
 }
 
 bool sw_solver_read_queries(const std::string& path, std::vector<std::string>* names, std::vector<std::string>* seqs,
@@ -714,6 +725,33 @@ std::vector<std::vector<sw_hit>> smith_waterman_cuda_batch_hits_sig(const std::v
     for (size_t q = 0; q < seqs.size(); ++q) {
         out[q].assign(rows.begin() + static_cast<int64_t>(q) * k, rows.begin() + static_cast<int64_t>(q) * k + nhits);
         (*sig)[q].assign(sigs.begin() + static_cast<int64_t>(q) * k, sigs.begin() + static_cast<int64_t>(q) * k + nhits);
+    }
+    return out;
+}
+
+std::vector<std::vector<sw_hit>> smith_waterman_cuda_batch_hits_ranked(const std::vector<std::string>& seqs,
+                                                                       FASTADatabase& db, int k, double max_evalue,
+                                                                       std::vector<std::vector<sw_sig>>* sig,
+                                                                       std::vector<int64_t>* n_pass,
+                                                                       std::vector<sw_calib>* calib) {
+    if (!sig || !n_pass || !calib)
+        throw std::invalid_argument("smith_waterman_cuda_batch_hits_ranked needs its three output vectors");
+    const size_t kk = static_cast<size_t>(std::max(k, 0));
+    std::vector<sw_hit> rows(seqs.size() * kk);
+    std::vector<sw_sig> sigs(seqs.size() * kk);
+    std::vector<int32_t> nhits(seqs.size(), 0);
+    calib->assign(seqs.size(), sw_calib{});
+    n_pass->assign(seqs.size(), 0);
+    batch_call(seqs, db, k, "sw_scan_batch_hits_ranked",
+               [&](sw_handle* h, sw_db* sdb, const uint8_t* qc, const int64_t* qoffs, int32_t nq, const sw_scoring* sc) {
+                   return sw_scan_batch_hits_ranked(h, sdb, qc, qoffs, nq, sc, k, max_evalue, 0, rows.data(), sigs.data(),
+                                                    nhits.data(), n_pass->data(), calib->data());
+               });
+    std::vector<std::vector<sw_hit>> out(seqs.size());
+    sig->assign(seqs.size(), std::vector<sw_sig>());
+    for (size_t q = 0; q < seqs.size(); ++q) {
+        out[q].assign(rows.begin() + static_cast<int64_t>(q) * k, rows.begin() + static_cast<int64_t>(q) * k + nhits[q]);
+        (*sig)[q].assign(sigs.begin() + static_cast<int64_t>(q) * k, sigs.begin() + static_cast<int64_t>(q) * k + nhits[q]);
     }
     return out;
 }

@@ -556,6 +556,83 @@ SW_API int sw_scan_batch_hits_sig(sw_handle* h, const sw_db* db, const uint8_t* 
                                   const int64_t* qoffsets, int32_t nq, const sw_scoring* sc, int32_t k,
                                   sw_hit* out, sw_sig* sig, int32_t* nhits, sw_calib* calib);
 
+/* ---- ranking by E-value, with an E-value cutoff (0.6.0) -------------------
+ * The _sig forms above rank by raw score and attach the significance to what
+ * came out; the statistic is length-regressed (z = (s - a - c ln L) / sigma),
+ * so their rows are not in E-value order and a short significant subject just
+ * under the k-th raw score is absent.  The _ranked forms rank by the statistic
+ * itself, as SSEARCH does, and take a threshold ("all hits with E <= 10").
+ * The step between the fit and the ranking is one more device pass over every
+ * subject.  The ranking is defined on integers, so host, device and tests
+ * agree bit for bit:
+ *   adj[L]   = llround(4096 c ln L) for L >= 1, adj[0] = 0, saturated to int32;
+ *              all zero when the calibration is DEGENERATE (sw_sig_rank_table).
+ *   r(s, L)  = clamp(s, 0, 2^20 - 1) * 4096 - adj[min(L, max_len)], saturated
+ *              to [SW_RANK_FLOOR, 2^32 - 1], SW_RANK_FLOOR = -2^32 + 1; a subject
+ *              with s <= 0 or L = 0 has r = SW_RANK_FLOOR (its E is n_db).
+ *              Ranking by r is ranking by z at 1/4096 of a score unit.
+ *   key      = r * 2^31 + (2^31 - 1 - id): r descending, then id ascending;
+ *              INT64_MIN = absent (past the database's end, or cut off).  The
+ *              keys go through sw_topk_keys_device's selection unchanged.
+ *   cutoff   : a subject passes iff r >= r_min, r_min = ceil(4096 (a + sigma
+ *              z_min)) with z_min solving E(z_min) = max_evalue in the E-value
+ *              formula above (sw_sig_rank_min).  max_evalue >= n_db or +inf:
+ *              SW_RANK_FLOOR (no cutoff).  DEGENERATE: SW_RANK_FLOOR if
+ *              max_evalue >= n_db, else 2^32 (nothing passes).  max_evalue <= 0
+ *              or NaN: SW_E_INVALID.  The cutoff is applied to the KEY: a
+ *              reported E-value (the exact double of sw_calib_sig) can sit a
+ *              relative 1e-4 either side of max_evalue at the edge.
+ *
+ *   sw_sig_rank_table, sw_sig_rank_min : host only, no handle; adj holds
+ *                  max_len + 1 entries.
+ *   sw_sig_topk_device : asynchronous on the handle's stream: uploads
+ *                  adj_host[0 .. max_len] (it must stay valid until the stream
+ *                  has passed the call's work), zeroes *count_out_dev, writes
+ *                  every subject's key (INT64_MIN below r_min) into the handle's
+ *                  workspace while counting the subjects that pass, exactly,
+ *                  into *count_out_dev (device uint32), then selects the k best
+ *                  keys, best first, into keys_out_dev[k] (INT64_MIN past the
+ *                  last passing subject).  scores_dev holds max_id + 1 slots as
+ *                  a scan wrote them; a slot no subject maps to is never read.
+ *                  1 <= k <= 4096.
+ *   sw_scan_hits_ranked, sw_scan_batch_hits_ranked : the scan and its table,
+ *                  the fit (first synchronisation), the key pass and selection
+ *                  (second), the hit-table rows of the selected ids (third).
+ *                  *nhits = min(k, *n_pass) rows in key order (out[nq][k],
+ *                  sig[nq][k], nhits[nq], n_pass[nq], calib[nq] for the batch;
+ *                  calib may be NULL), sig[i] = sw_calib_sig(calib, row i's
+ *                  score, row i's s_len); *n_pass, the subjects that pass the
+ *                  cutoff, may exceed k: the list was truncated.  max_evalue
+ *                  +inf: no cutoff.  An empty database gives 0 and 0.  The fit
+ *                  must precede the ranking, so a batch cannot share one score
+ *                  row: it keeps G = max(1, min(nq, score_bytes / (4 slots)))
+ *                  rows (slots = max_id + 1; score_bytes 0 = 256 MiB) and runs
+ *                  groups of G queries, each group's scans and tables, one
+ *                  synchronisation, its fits, key passes and selections; then
+ *                  one synchronisation and every query's rows in one launch
+ *                  sequence: three synchronisations when the rows fit.
+ *   sw_scan_pssm_topk_ranked : the same for a PSSM; there is no PSSM hit table,
+ *                  so a device gather writes ids[i], scores[i] and the
+ *                  significance comes from the subject's length; two
+ *                  synchronisations.
+ * Out of scope: sw_group_*, composition-based score adjustment, a PSSM hit
+ * table.                                                                     */
+#define SW_RANK_SCALE 4096
+#define SW_RANK_FLOOR (-4294967295LL)   /* -2^32 + 1 */
+#define SW_RANK_NONE 4294967296LL       /* 2^32: an r_min nothing passes */
+SW_API int sw_sig_rank_table(const sw_calib* calib, int32_t max_len, int32_t* adj);
+SW_API int sw_sig_rank_min(const sw_calib* calib, double max_evalue, int64_t* r_min);
+SW_API int sw_sig_topk_device(sw_handle* h, const sw_db* db, const int32_t* scores_dev, const int32_t* adj_host,
+                              int32_t max_len, int64_t r_min, int32_t k, int64_t* keys_out_dev,
+                              uint32_t* count_out_dev);
+SW_API int sw_scan_hits_ranked(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen,
+                               const sw_scoring* sc, int32_t k, double max_evalue, sw_hit* out, sw_sig* sig,
+                               int32_t* nhits, int64_t* n_pass, sw_calib* calib);
+SW_API int sw_scan_batch_hits_ranked(sw_handle* h, const sw_db* db, const uint8_t* queries,
+                                     const int64_t* qoffsets, int32_t nq, const sw_scoring* sc, int32_t k,
+                                     double max_evalue, int64_t score_bytes, sw_hit* out, sw_sig* sig,
+                                     int32_t* nhits, int64_t* n_pass, sw_calib* calib);
+
 /* ---- profile (PSSM) queries ------------------------------------------------
  * A position-specific scoring matrix in the place of a query: a [qlen][25]
  * int8 table, rows[i*25 + c] = score of subject residue code c at query
@@ -594,6 +671,12 @@ SW_API int sw_align_pssm(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_
 /* sw_scan_pssm_topk and the scan's calibration (see "E-values and bit scores"). */
 SW_API int sw_scan_pssm_topk_calib(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open,
                                    int32_t gap_extend, int32_t k, int64_t* keys_host, sw_calib* calib);
+/* A PSSM scan ranked by E-value (see "ranking by E-value"): ids[k], scores[k],
+ * sig[k], of which the first *nhits = min(k, *n_pass) are written. */
+SW_API int sw_scan_pssm_topk_ranked(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open,
+                                    int32_t gap_extend, int32_t k, double max_evalue, int32_t* ids,
+                                    int32_t* scores, sw_sig* sig, int32_t* nhits, int64_t* n_pass,
+                                    sw_calib* calib);
 
 /* ---- single pair ---------------------------------------------------------
  * One query against one subject on the GPU (wavefront kernel); the GPU

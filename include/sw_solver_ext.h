@@ -82,6 +82,13 @@ std::vector<sw_hit> smith_waterman_cuda_hits(FASTAQuery& query, FASTADatabase& d
  * (sw_amd.h sw_scan_hits_sig; `main --hits K --evalue`). */
 std::vector<sw_hit> smith_waterman_cuda_hits_sig(FASTAQuery& query, FASTADatabase& db, int k, std::vector<sw_sig>* sig,
                                                  sw_calib* calib);
+/* The same ranked by E-value instead of raw score, with an E-value cutoff
+ * (sw_amd.h sw_scan_hits_ranked; `main --hits K --evalue --rank evalue
+ * [--max-evalue X]`): the rows of the min(k, *n_pass) most significant
+ * subjects with E <= max_evalue (+infinity: no cutoff), in E-value order;
+ * *n_pass (may be NULL), the subjects that pass, may exceed k. */
+std::vector<sw_hit> smith_waterman_cuda_hits_ranked(FASTAQuery& query, FASTADatabase& db, int k, double max_evalue,
+                                                    std::vector<sw_sig>* sig, int64_t* n_pass, sw_calib* calib);
 
 /* Batches of queries (sw_amd.h sw_scan_batch_topk / sw_scan_batch_hits;
  * `main --queries FILE`).  sw_solver_read_queries reads a multi-record FASTA
@@ -108,6 +115,14 @@ std::vector<std::vector<sw_hit> > smith_waterman_cuda_batch_hits_sig(const std::
                                                                      FASTADatabase& db, int k,
                                                                      std::vector<std::vector<sw_sig> >* sig,
                                                                      std::vector<sw_calib>* calib);
+/* The batch form of smith_waterman_cuda_hits_ranked (sw_amd.h
+ * sw_scan_batch_hits_ranked): (*n_pass)[query] as above; a query's row count
+ * is its own. */
+std::vector<std::vector<sw_hit> > smith_waterman_cuda_batch_hits_ranked(const std::vector<std::string>& seqs,
+                                                                        FASTADatabase& db, int k, double max_evalue,
+                                                                        std::vector<std::vector<sw_sig> >* sig,
+                                                                        std::vector<int64_t>* n_pass,
+                                                                        std::vector<sw_calib>* calib);
 
 /* Profile (PSSM) queries (sw_amd.h sw_pssm_*; `main --pssm FILE`).
  * sw_solver_read_pssm reads a text PSSM into rows ([positions][25] int8 in
