@@ -19,6 +19,10 @@
 // SWSolver.cu:7) unless sw_solver_set_scoring chose another matrix / gap
 // model (`main --matrix --gap-open --gap-extend`); smith_waterman_cuda_topk
 // returns only the k best subjects, ranked on the device (`main --topk`).
+//
+// Every entry point, and `main` through sw_solver_search, is one request to
+// search() below: the subjects (a FASTADatabase flattened, or a .swdb file
+// loaded), the timed stages, and the one library call the request names.
 #include <sys/time.h>
 
 #include <algorithm>
@@ -28,6 +32,7 @@
 #include <cstring>
 #include <fstream>
 #include <mutex>
+#include <numeric>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -36,14 +41,17 @@
 
 #include "SWSolver.h"
 #include "SWSolver_char.h"
+#include "sw_abi_ptr.h"
 #include "sw_amd.h"
 #include "sw_solver_ext.h"
 
 namespace {
 
 std::mutex g_mu;
-sw_handle* g_handle = nullptr;
-sw_group* g_group = nullptr;
+// process-wide, and alive until the process ends: torn down from a static
+// destructor they would race the HIP runtime's own
+sw_handle_ptr& g_handle = *new sw_handle_ptr;
+sw_group_ptr& g_group = *new sw_group_ptr;
 int g_gpus = 0;  // 0: $SW_GPUS or 1
 sw_solver_timing g_timing = {};
 // the scoring of smith_waterman_cuda[_topk]; custom = false: the reference's
@@ -64,6 +72,14 @@ double now_s() {
     return static_cast<double>(tv.tv_usec) / 1000000 + tv.tv_sec;
 }
 
+// The wall time of a scope, added to one field of g_timing.
+struct Stage {
+    double& field;
+    const double t0 = now_s();
+    explicit Stage(double& f) : field(f) {}
+    ~Stage() { field += now_s() - t0; }
+};
+
 int gpus() {
     if (g_gpus > 0) return g_gpus;
     const char* e = std::getenv("SW_GPUS");
@@ -74,16 +90,18 @@ int gpus() {
 sw_handle* handle() {
     if (!g_handle) {
         const char* dev = std::getenv("SW_DEVICE");
-        check(sw_create(dev ? std::atoi(dev) : 0, &g_handle), "sw_create");
+        sw_handle* h = nullptr;
+        check(sw_create(dev ? std::atoi(dev) : 0, &h), "sw_create");
+        g_handle.reset(h);
     }
-    return g_handle;
+    return g_handle.get();
 }
 
 // The group over the first gpus() devices ($SW_DEVICES="a,b,..." overrides
 // the list, e.g. "0,0" to run the sharded path on a one-GPU machine).
 sw_group* group() {
     const int n = gpus();
-    if (g_group) return g_group;
+    if (g_group) return g_group.get();
     std::vector<int32_t> devs;
     if (const char* e = std::getenv("SW_DEVICES")) {
         std::string s(e);
@@ -96,14 +114,30 @@ sw_group* group() {
         }
     }
     for (int d = static_cast<int>(devs.size()); d < n; ++d) devs.push_back(d);
-    check(sw_group_create(devs.data(), n, &g_group), "sw_group_create");
-    return g_group;
+    sw_group* g = nullptr;
+    check(sw_group_create(devs.data(), n, &g), "sw_group_create");
+    g_group.reset(g);
+    return g;
 }
 
-struct Flat {
-    std::vector<uint8_t> residues;
+// The subjects of one search: their record ids in the database's own order,
+// what the report needs, and the database itself — loaded from a file, or
+// uploaded by search() from the flattened residues.
+struct Subjects {
+    std::vector<uint8_t> residues;  // a FASTA's, encoded; empty for a file
     std::vector<int64_t> offsets{0};
-    std::vector<int> record_ids;  // FASTA record id of each flattened subject
+    std::vector<int32_t> ids;    // record id of each subject
+    std::vector<int64_t> order;  // the plain scan's report order: indices into ids
+    sw_db_ptr db;
+    sw_gdb_ptr gdb;  // ... or sharded over the group
+    bool from_file = false;
+    int64_t max_id = -1;                        // a file's scores are indexed by record id
+    int64_t num_subjects = 0, padded_sum = 0;  // METRICS: the FASTA parser's counts (TILE_SIZE padding)
+
+    Subjects(FASTADatabase& fdb, bool strip_pad);
+    explicit Subjects(const std::string& path);
+    int64_t n() const { return static_cast<int64_t>(ids.size()); }
+    int64_t score_slot(int64_t k) const { return from_file ? ids[static_cast<size_t>(k)] : k; }
 };
 
 // Flatten in the reference's reporting order; the encoding (SWSolver.cu:91-
@@ -113,16 +147,15 @@ struct Flat {
 // written.  Under the reference's BLOSUM50 the pad scores 0 and changes no
 // score, so it is kept there; other scorings (BLOSUM62: '*' +1 against '*')
 // and the binary database files get the subjects as written.
-Flat flatten(FASTADatabase& db, bool strip_pad = false) {
-    Flat f;
+Subjects::Subjects(FASTADatabase& fdb, bool strip_pad) {
+    Stage flatten(g_timing.flatten_s);
     std::vector<const subject_sequence*> subj;
-    subj.reserve(db.numSubjects > 0 ? static_cast<size_t>(db.numSubjects) : 0);
-    for (auto it = db.parsedDB.rbegin(); it != db.parsedDB.rend(); ++it)
+    subj.reserve(fdb.numSubjects > 0 ? static_cast<size_t>(fdb.numSubjects) : 0);
+    for (auto it = fdb.parsedDB.rbegin(); it != fdb.parsedDB.rend(); ++it)
         for (const subject_sequence& s : it->second) subj.push_back(&s);
     const size_t n = subj.size();
-    f.offsets.resize(n + 1);
-    f.record_ids.resize(n);
-    f.offsets[0] = 0;
+    offsets.resize(n + 1);
+    ids.resize(n);
     auto len_of = [&](size_t k) {
         const std::string& s = subj[k]->sequence;
         size_t m = s.size();
@@ -130,10 +163,10 @@ Flat flatten(FASTADatabase& db, bool strip_pad = false) {
         return m;
     };
     for (size_t k = 0; k < n; ++k) {
-        f.offsets[k + 1] = f.offsets[k] + static_cast<int64_t>(len_of(k));
-        f.record_ids[k] = subj[k]->id;
+        offsets[k + 1] = offsets[k] + static_cast<int64_t>(len_of(k));
+        ids[k] = subj[k]->id;
     }
-    f.residues.resize(static_cast<size_t>(f.offsets[n]));
+    residues.resize(static_cast<size_t>(offsets[n]));
     uint8_t probe;
     check(sw_encode("A", 1, &probe), "sw_encode");  // the code table exists before the threads start
     unsigned nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
@@ -144,77 +177,256 @@ Flat flatten(FASTADatabase& db, bool strip_pad = false) {
         th.emplace_back([&, t] {
             for (size_t k = t; k < n; k += nt) {
                 const std::string& s = subj[k]->sequence;
-                const int r = sw_encode(s.data(), f.offsets[k + 1] - f.offsets[k], f.residues.data() + f.offsets[k]);
+                const int r = sw_encode(s.data(), offsets[k + 1] - offsets[k], residues.data() + offsets[k]);
                 if (r) rc[t] = r;
             }
         });
     for (auto& x : th) x.join();
     for (int r : rc) check(r, "sw_encode");
-    return f;
+    order.resize(n);
+    std::iota(order.begin(), order.end(), int64_t{0});
+    num_subjects = fdb.numSubjects;
+    padded_sum = fdb.subjectLengthSum;
 }
 
-// The encoded query.  The reference pads it with '/' to a multiple of
-// TILE_SIZE (SWSolver.cu:267-269); '/' encodes as '*', whose BLOSUM50 row is
-// all zero, so under the reference's scoring the padding cannot change a
-// score and is kept for the literal drop-in.  Other scorings (BLOSUM62 scores
-// '*' -4 / +1) get the query as written, and so does the _char path
-// (SWSolver_char.cu:195-198 copies it as is).
-std::vector<uint8_t> encode_query(FASTAQuery& query, bool pad) {
-    std::string q = query.get_buffer();
-    while (pad && q.size() % TILE_SIZE != 0) q += "/";
-    std::vector<uint8_t> qc(q.size());
-    check(sw_encode(q.data(), static_cast<int64_t>(q.size()), qc.data()), "sw_encode");
-    return qc;
-}
-
-// Scores of the flattened subjects (index k), under g_sc (by default the
-// reference's: BLOSUM50 of SWSolver.cu:54-81 with linear gap 2, SWSolver.cu:7).
-// char_compat: the _char path's scoring (SW_MATRIX_BLOSUM50_CHAR, no query
-// padding).
-std::vector<int32_t> score_all(FASTAQuery& query, const Flat& f, bool char_compat = false) {
-    const std::vector<uint8_t> qc = encode_query(query, !char_compat && !g_sc.custom);
-    const int64_t n = static_cast<int64_t>(f.record_ids.size());
-    std::vector<int32_t> scores(static_cast<size_t>(n), 0);
-    g_timing.gpus = gpus();
-    if (n == 0) return scores;
-    int8_t mat[625];
-    if (char_compat) check(sw_builtin_matrix(SW_MATRIX_BLOSUM50_CHAR, mat), "sw_builtin_matrix");
-    const sw_scoring sc = char_compat ? sw_scoring{mat, 2, 2}
-                                      : sw_scoring{g_sc.has_matrix ? g_sc.mat : nullptr, g_sc.go, g_sc.ge};
-    // device start-up (HIP runtime, handle or group) is timed on its own
-    double t0 = now_s();
-    sw_handle* h = gpus() == 1 ? handle() : nullptr;
-    sw_group* g = gpus() == 1 ? nullptr : group();
-    g_timing.init_s = now_s() - t0;
-    t0 = now_s();
-    if (h) {
-        sw_db* db = nullptr;
-        check(sw_db_create(h, f.residues.data(), f.offsets.data(), n, nullptr, &db), "sw_db_create");
-        g_timing.upload_s = now_s() - t0;
-        t0 = now_s();
-        const int rc = sw_scan(h, db, qc.data(), static_cast<int32_t>(qc.size()), &sc, scores.data());
-        g_timing.scan_s = now_s() - t0;
-        sw_db_free(db);
-        check(rc, "sw_scan");
-    } else {
-        sw_gdb* db = nullptr;
-        check(sw_group_db_create(g, f.residues.data(), f.offsets.data(), n, nullptr, &db), "sw_group_db_create");
-        g_timing.upload_s = now_s() - t0;
-        t0 = now_s();
-        const int rc = sw_group_scan(g, db, qc.data(), static_cast<int32_t>(qc.size()), &sc, scores.data());
-        g_timing.scan_s = now_s() - t0;
-        sw_group_db_free(db);
-        check(rc, "sw_group_scan");
+// A .swdb file holds the flattened order, the record ids and the subjects as
+// written (sw_save_fasta_db).  The report order is the reference's: padded
+// length descending, file (= record id) order within a length
+// (SWSolver.cu:309,384-390); the padded sizes are the FASTA parser's
+// (TILE_SIZE; older files hold '/'-padded subjects: the same sums).
+Subjects::Subjects(const std::string& path) : from_file(true) {
+    sw_handle* h = nullptr;
+    {
+        Stage init(g_timing.init_s);
+        h = handle();
     }
-    return scores;
+    {
+        Stage upload(g_timing.upload_s);
+        sw_db* loaded = nullptr;
+        check(sw_db_load(h, path.c_str(), &loaded), "sw_db_load");
+        db.reset(loaded);
+    }
+    sw_db_stats st;
+    check(sw_db_get_stats(db.get(), &st), "sw_db_get_stats");
+    std::vector<int64_t> lens(static_cast<size_t>(st.n_subjects));
+    ids.resize(lens.size());
+    check(sw_db_subjects(db.get(), lens.data(), ids.data()), "sw_db_subjects");
+    auto padded = [&](int64_t k) { return roundUp(static_cast<int>(lens[static_cast<size_t>(k)]), TILE_SIZE); };
+    order.resize(lens.size());
+    std::iota(order.begin(), order.end(), int64_t{0});
+    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+        return padded(a) != padded(b) ? padded(a) > padded(b) : ids[a] < ids[b];
+    });
+    for (int64_t k = 0; k < st.n_subjects; ++k) padded_sum += padded(k);
+    num_subjects = st.n_subjects;
+    max_id = st.max_id;
 }
 
-Flat timed_flatten(FASTADatabase& db, bool strip_pad) {
+std::vector<uint8_t> encode(const std::string& s) {
+    std::vector<uint8_t> codes(s.size());
+    check(sw_encode(s.data(), static_cast<int64_t>(s.size()), codes.data()), "sw_encode");
+    return codes;
+}
+
+// The queries as written, concatenated (sw_scan_batch's form).
+void concat_queries(const std::vector<std::string>& seqs, std::vector<uint8_t>* codes, std::vector<int64_t>* offs) {
+    offs->assign(seqs.size() + 1, 0);
+    for (size_t q = 0; q < seqs.size(); ++q) (*offs)[q + 1] = (*offs)[q] + static_cast<int64_t>(seqs[q].size());
+    codes->resize(static_cast<size_t>(offs->back()));
+    for (size_t q = 0; q < seqs.size(); ++q)
+        check(sw_encode(seqs[q].data(), static_cast<int64_t>(seqs[q].size()), codes->data() + (*offs)[q]), "sw_encode");
+}
+
+// A device top-K key (sw_amd.h sw_scan_topk) as (record id, score); the keys
+// of one query end at k or at the first INT64_MIN (fewer subjects than k).
+seqid_score decode_key(int64_t key) {
+    return std::make_pair(static_cast<int>((int64_t{1} << 31) - 1 - (key & 0xffffffff)), static_cast<int>(key >> 32));
+}
+
+// Score descending, record id ascending: the device top-K's order, for a k
+// beyond its 4096 or record ids it cannot carry (a headerless file's -1).
+void rank_on_host(std::vector<seqid_score>* v, int k) {
+    const size_t kk = std::min<size_t>(v->size(), static_cast<size_t>(k));
+    std::partial_sort(v->begin(), v->begin() + kk, v->end(), [](const seqid_score& a, const seqid_score& b) {
+        return a.second != b.second ? a.second > b.second : a.first < b.first;
+    });
+    v->resize(kk);
+}
+
+// Query q's n rows of a table that holds k per query.
+template <class T>
+std::vector<T> rows_of(const std::vector<T>& all, size_t q, int k, int32_t n) {
+    const auto at = all.begin() + static_cast<int64_t>(q) * k;
+    return std::vector<T>(at, at + n);
+}
+
+// The two departures of smith_waterman_cuda_char from a plain scan: the
+// subjects keep the parser's padding under any scoring, and with
+// SW_CHAR_COMPAT=1 the scoring is the _char path's own table.
+enum class CharPath { NO, ORDER, TABLE };
+
+// The library entry point a request goes to, as the error texts name it (a
+// loaded file's have never said _pssm or _sig).
+std::string entry_name(const sw_search_request& rq, bool from_file, bool group, bool all_scores) {
+    std::string name = group ? "sw_group" : "sw_scan";
+    if (rq.queries) name += "_batch";
+    if (rq.pssm && !from_file) name += "_pssm";
+    if (all_scores) name += group ? "_scan" : "";
+    else name += rq.mode == sw_search_request::HITS ? "_hits" : "_topk";
+    if (rq.ranked) name += "_ranked";
+    else if (rq.evalue && !from_file) name += "_sig";
+    return name;
+}
+
+// One search: exactly one of fdb / file names the subjects.
+sw_search_result search(FASTADatabase* fdb, const std::string& file, const sw_search_request& rq,
+                        CharPath cp = CharPath::NO) {
+    const bool batch = rq.queries != nullptr, hits = rq.mode == sw_search_request::HITS;
+    const int k = rq.k;
+    if (!rq.query + !rq.queries + !rq.pssm != 2)
+        throw std::invalid_argument("a search takes one of a query, a batch of queries and a PSSM");
+    if ((hits && rq.pssm) || (rq.evalue && !hits) || (rq.ranked && !rq.evalue))
+        throw std::invalid_argument("significances belong to a hit table, ranking by them to significances, "
+                                    "and a hit table to a query or a batch");
+    if (batch && (k < 1 || k > 4096)) throw std::invalid_argument("a batch of queries needs 1 <= k <= 4096");
+    if (hits && (k < 1 || k > 4096)) throw std::invalid_argument("the hit table needs 1 <= k <= 4096");
+    std::lock_guard<std::mutex> lock(g_mu);  // the reference is not re-entrant either
     g_timing = sw_solver_timing{};
-    const double t0 = now_s();
-    Flat f = flatten(db, strip_pad);
-    g_timing.flatten_s = now_s() - t0;
-    return f;
+    // Subjects and query as written, or with the '/' padding of the parser
+    // and of SWSolver.cu:267-269?  The padding scores 0 under the reference's
+    // table alone, so a set scoring drops it; a hit table's coordinates are
+    // those of the sequences as written; batches and PSSMs never had it.
+    const bool as_written = hits || batch || rq.pssm || g_sc.custom;
+    Subjects s = fdb ? Subjects(*fdb, as_written && cp == CharPath::NO) : Subjects(file);
+    const double t_solve = now_s();  // a loaded file's solve_s: the search once the subjects are in hand
+    const int64_t n = s.n();
+    const bool no_id = std::any_of(s.ids.begin(), s.ids.end(), [](int32_t id) { return id < 0; });
+    if (fdb && no_id && (hits || batch))
+        throw std::invalid_argument(batch ? "a batch of queries needs record ids (a FASTA header per subject)"
+                                          : "the hit table needs record ids (a FASTA header per subject)");
+    // every score to the host: the plain scan, and a top-K ranked there
+    const bool host_rank = rq.mode == sw_search_request::TOPK && (k > 4096 || (fdb && (no_id || n == 0)));
+    const bool all_scores = rq.mode == sw_search_request::SCORES || host_rank;
+
+    std::vector<uint8_t> qc;
+    std::vector<int64_t> qoffs;
+    if (batch) concat_queries(*rq.queries, &qc, &qoffs);
+    else if (rq.query) {
+        std::string q = *rq.query;
+        while (!as_written && cp != CharPath::TABLE && q.size() % TILE_SIZE != 0) q += "/";
+        qc = encode(q);
+    }
+    const int32_t ql = static_cast<int32_t>(qc.size()), nq = batch ? static_cast<int32_t>(rq.queries->size()) : 1;
+    int8_t char_mat[625];
+    if (cp == CharPath::TABLE) check(sw_builtin_matrix(SW_MATRIX_BLOSUM50_CHAR, char_mat), "sw_builtin_matrix");
+    const sw_scoring sc = cp == CharPath::TABLE ? sw_scoring{char_mat, 2, 2}
+                                                : sw_scoring{g_sc.has_matrix ? g_sc.mat : nullptr, g_sc.go, g_sc.ge};
+
+    sw_search_result r;
+    r.num_subjects = s.num_subjects;
+    r.padded_residues = s.padded_sum;
+    r.scores.resize(hits ? 0 : static_cast<size_t>(nq));
+    // only a FASTA's plain scan and top-K are sharded over several GPUs
+    const bool sharded = fdb && rq.query && !hits && gpus() > 1;
+    g_timing.gpus = sharded ? gpus() : 1;
+    if (n == 0 && all_scores && !rq.pssm) return r;
+
+    sw_handle* h = nullptr;
+    sw_group* g = nullptr;
+    {
+        Stage init(g_timing.init_s);  // device start-up (HIP runtime, handle or group) is timed on its own
+        if (sharded) g = group();
+        else h = handle();
+    }
+    sw_pssm_ptr pssm;
+    {
+        Stage upload(g_timing.upload_s);
+        const int32_t* ids = all_scores ? nullptr : s.ids.data();  // the top-K and the hit table report record ids
+        if (fdb && sharded) {
+            sw_gdb* gdb = nullptr;
+            check(sw_group_db_create(g, s.residues.data(), s.offsets.data(), n, ids, &gdb), "sw_group_db_create");
+            s.gdb.reset(gdb);
+        } else if (fdb) {
+            sw_db* db = nullptr;
+            check(sw_db_create(h, s.residues.data(), s.offsets.data(), n, ids, &db), "sw_db_create");
+            s.db.reset(db);
+        }
+        if (rq.pssm) {
+            sw_pssm* p = nullptr;
+            check(sw_pssm_create(h, rq.pssm->data(), static_cast<int32_t>(rq.pssm->size() / 25), &p), "sw_pssm_create");
+            pssm.reset(p);
+        }
+    }
+
+    const sw_db* db = s.db.get();
+    const size_t table = hits ? static_cast<size_t>(nq) * static_cast<size_t>(k) : 0;
+    std::vector<int32_t> scores(static_cast<size_t>(all_scores ? (s.from_file ? s.max_id + 1 : n) : 0), 0);
+    std::vector<int64_t> keys(all_scores || hits ? 0 : static_cast<size_t>(nq) * static_cast<size_t>(k));
+    std::vector<sw_hit> rows(table);
+    std::vector<sw_sig> sigs(rq.evalue ? table : 0);
+    std::vector<int32_t> nhits(hits ? static_cast<size_t>(nq) : 0, 0);  // a ranked query's row count is its own
+    r.calibs.resize(rq.evalue ? static_cast<size_t>(nq) : 0);
+    r.n_pass.resize(rq.ranked ? static_cast<size_t>(nq) : 0);
+    int rc = SW_OK;
+    {
+        Stage scan(g_timing.scan_s);
+        if (all_scores) {
+            if (n == 0) rc = SW_OK;
+            else if (rq.pssm) rc = sw_scan_pssm(h, db, pssm.get(), g_sc.go, g_sc.ge, scores.data());
+            else if (sharded) rc = sw_group_scan(g, s.gdb.get(), qc.data(), ql, &sc, scores.data());
+            else rc = sw_scan(h, db, qc.data(), ql, &sc, scores.data());
+        } else if (!hits) {
+            if (batch) rc = sw_scan_batch_topk(h, db, qc.data(), qoffs.data(), nq, &sc, k, keys.data());
+            else if (rq.pssm) rc = sw_scan_pssm_topk(h, db, pssm.get(), g_sc.go, g_sc.ge, k, keys.data());
+            else if (sharded) rc = sw_group_topk(g, s.gdb.get(), qc.data(), ql, &sc, k, keys.data());
+            else rc = sw_scan_topk(h, db, qc.data(), ql, &sc, k, keys.data());
+        } else if (batch) {
+            if (rq.ranked)
+                rc = sw_scan_batch_hits_ranked(h, db, qc.data(), qoffs.data(), nq, &sc, k, rq.max_evalue, 0, rows.data(),
+                                               sigs.data(), nhits.data(), r.n_pass.data(), r.calibs.data());
+            else if (rq.evalue)
+                rc = sw_scan_batch_hits_sig(h, db, qc.data(), qoffs.data(), nq, &sc, k, rows.data(), sigs.data(),
+                                            nhits.data(), r.calibs.data());
+            else rc = sw_scan_batch_hits(h, db, qc.data(), qoffs.data(), nq, &sc, k, rows.data(), nhits.data());
+            if (!rq.ranked) std::fill(nhits.begin(), nhits.end(), nhits.empty() ? 0 : nhits[0]);  // one count for all
+        } else if (rq.ranked) {
+            rc = sw_scan_hits_ranked(h, db, qc.data(), ql, &sc, k, rq.max_evalue, rows.data(), sigs.data(), nhits.data(),
+                                     r.n_pass.data(), r.calibs.data());
+        } else if (rq.evalue) {
+            rc = sw_scan_hits_sig(h, db, qc.data(), ql, &sc, k, rows.data(), sigs.data(), nhits.data(), r.calibs.data());
+        } else {
+            rc = sw_scan_hits(h, db, qc.data(), ql, &sc, k, rows.data(), nhits.data());
+        }
+    }
+    check(rc, entry_name(rq, s.from_file, sharded, all_scores).c_str());
+
+    if (all_scores) {
+        r.scores[0].reserve(static_cast<size_t>(n));
+        for (int64_t i : s.order)
+            r.scores[0].push_back(std::make_pair(static_cast<int>(s.ids[static_cast<size_t>(i)]),
+                                                 static_cast<int>(scores[static_cast<size_t>(s.score_slot(i))])));
+        if (host_rank) rank_on_host(&r.scores[0], k);
+    }
+    for (size_t q = 0; q < static_cast<size_t>(nq) && !keys.empty(); ++q)
+        for (int i = 0; i < k && keys[q * static_cast<size_t>(k) + i] != INT64_MIN; ++i)
+            r.scores[q].push_back(decode_key(keys[q * static_cast<size_t>(k) + i]));
+    for (size_t q = 0; q < nhits.size(); ++q) {
+        r.rows.push_back(rows_of(rows, q, k, nhits[q]));
+        if (rq.evalue) r.sigs.push_back(rows_of(sigs, q, k, nhits[q]));
+    }
+    r.solve_s = now_s() - t_solve;
+    return r;
+}
+
+sw_search_request request(const std::string* query, const std::vector<std::string>* queries,
+                          const std::vector<int8_t>* pssm, sw_search_request::Mode mode, int k) {
+    sw_search_request rq = {};
+    rq.query = query;
+    rq.queries = queries;
+    rq.pssm = pssm;
+    rq.mode = mode;
+    rq.k = k;
+    return rq;
 }
 
 // One matrix entry of a text matrix file.
@@ -412,202 +624,6 @@ bool sw_solver_read_pssm(const std::string& path, std::vector<int8_t>* rows, std
     return true;
 }
 
-std::vector<seqid_score> smith_waterman_cuda_pssm(const std::vector<int8_t>& rows, FASTADatabase& db, int k) {
-    if (k < 0) throw std::invalid_argument("top-k needs k >= 0");
-    if (rows.size() % 25 != 0) throw std::invalid_argument("a PSSM holds 25 entries per row");
-    std::lock_guard<std::mutex> lock(g_mu);
-    const Flat f = timed_flatten(db, true);  // the subjects as written, as under any set scoring
-    const int64_t n = static_cast<int64_t>(f.record_ids.size());
-    const int32_t qlen = static_cast<int32_t>(rows.size() / 25);
-    std::vector<seqid_score> out;
-    g_timing.gpus = 1;
-    double t0 = now_s();
-    sw_handle* h = handle();
-    g_timing.init_s = now_s() - t0;
-    t0 = now_s();
-    bool ids_ok = n > 0;
-    for (int id : f.record_ids) ids_ok = ids_ok && id >= 0;
-    const bool device_topk = k > 0 && k <= 4096 && ids_ok;
-    std::vector<int32_t> ids(f.record_ids.begin(), f.record_ids.end());
-    sw_db* sdb = nullptr;
-    sw_pssm* p = nullptr;
-    check(sw_db_create(h, f.residues.data(), f.offsets.data(), n, device_topk ? ids.data() : nullptr, &sdb),
-          "sw_db_create");
-    int rc = sw_pssm_create(h, rows.data(), qlen, &p);
-    g_timing.upload_s = now_s() - t0;
-    t0 = now_s();
-    std::vector<int64_t> keys(static_cast<size_t>(device_topk ? k : 0));
-    std::vector<int32_t> scores(static_cast<size_t>(device_topk ? 0 : n), 0);
-    const char* what = "sw_pssm_create";
-    if (rc == SW_OK && device_topk) {
-        what = "sw_scan_pssm_topk";
-        rc = sw_scan_pssm_topk(h, sdb, p, g_sc.go, g_sc.ge, k, keys.data());
-    } else if (rc == SW_OK && n > 0) {
-        what = "sw_scan_pssm";
-        rc = sw_scan_pssm(h, sdb, p, g_sc.go, g_sc.ge, scores.data());
-    }
-    g_timing.scan_s = now_s() - t0;
-    sw_pssm_free(p);
-    sw_db_free(sdb);
-    check(rc, what);
-    if (device_topk) {
-        for (int64_t key : keys) {
-            if (key == INT64_MIN) break;  // fewer subjects than k
-            out.push_back(std::make_pair(static_cast<int>((int64_t{1} << 31) - 1 - (key & 0xffffffff)),
-                                         static_cast<int>(key >> 32)));
-        }
-        return out;
-    }
-    for (int64_t i = 0; i < n; ++i) out.push_back(std::make_pair(f.record_ids[i], scores[i]));
-    if (k > 0) {  // beyond the device top-K's k (or a headerless file's id -1): ranked here
-        const size_t kk = std::min<size_t>(out.size(), static_cast<size_t>(k));
-        std::partial_sort(out.begin(), out.begin() + kk, out.end(), [](const seqid_score& a, const seqid_score& b) {
-            return a.second != b.second ? a.second > b.second : a.first < b.first;
-        });
-        out.resize(kk);
-    }
-    return out;
-}
-
-void sw_solver_set_scoring(const int8_t* matrix625, int gap_open, int gap_extend) {
-    if (gap_open < 1 || gap_open > 1000 || gap_extend < 1 || gap_extend > 1000)
-        throw std::invalid_argument("gap penalties must be in 1..1000");
-    if (matrix625)
-        for (int k = 0; k < 625; ++k)
-            if (matrix625[k] < -100 || matrix625[k] > 100)
-                throw std::invalid_argument("matrix entries must be in -100..100");
-    std::lock_guard<std::mutex> lock(g_mu);
-    g_sc = SolverScoring{};
-    g_sc.custom = true;
-    g_sc.has_matrix = matrix625 != nullptr;
-    if (matrix625) std::memcpy(g_sc.mat, matrix625, 625);
-    g_sc.go = gap_open;
-    g_sc.ge = gap_extend;
-}
-
-void sw_solver_reset_scoring() {
-    std::lock_guard<std::mutex> lock(g_mu);
-    g_sc = SolverScoring{};
-}
-
-std::vector<seqid_score> smith_waterman_cuda_topk(FASTAQuery& query, FASTADatabase& db, int k) {
-    if (k < 1) throw std::invalid_argument("top-k needs k >= 1");
-    std::lock_guard<std::mutex> lock(g_mu);
-    const Flat f = timed_flatten(db, g_sc.custom);
-    const int64_t n = static_cast<int64_t>(f.record_ids.size());
-    std::vector<seqid_score> out;
-    bool ids_ok = n > 0;
-    for (int id : f.record_ids) ids_ok = ids_ok && id >= 0;
-    if (k > 4096 || !ids_ok) {
-        // beyond the device top-K's k (or a headerless file's id -1): every
-        // score to the host, ranked there (score desc, id asc)
-        const std::vector<int32_t> scores = score_all(query, f);
-        for (int64_t i = 0; i < n; ++i) out.push_back(std::make_pair(f.record_ids[i], scores[i]));
-        const size_t kk = std::min<size_t>(out.size(), static_cast<size_t>(k));
-        std::partial_sort(out.begin(), out.begin() + kk, out.end(), [](const seqid_score& a, const seqid_score& b) {
-            return a.second != b.second ? a.second > b.second : a.first < b.first;
-        });
-        out.resize(kk);
-        return out;
-    }
-    const std::vector<uint8_t> qc = encode_query(query, !g_sc.custom);
-    const sw_scoring sc = {g_sc.has_matrix ? g_sc.mat : nullptr, g_sc.go, g_sc.ge};
-    std::vector<int32_t> ids(f.record_ids.begin(), f.record_ids.end());
-    std::vector<int64_t> keys(static_cast<size_t>(k));
-    g_timing.gpus = gpus();
-    double t0 = now_s();
-    sw_handle* h = gpus() == 1 ? handle() : nullptr;
-    sw_group* g = gpus() == 1 ? nullptr : group();
-    g_timing.init_s = now_s() - t0;
-    t0 = now_s();
-    const int32_t ql = static_cast<int32_t>(qc.size());
-    if (h) {
-        sw_db* sdb = nullptr;
-        check(sw_db_create(h, f.residues.data(), f.offsets.data(), n, ids.data(), &sdb), "sw_db_create");
-        g_timing.upload_s = now_s() - t0;
-        t0 = now_s();
-        const int rc = sw_scan_topk(h, sdb, qc.data(), ql, &sc, k, keys.data());
-        g_timing.scan_s = now_s() - t0;
-        sw_db_free(sdb);
-        check(rc, "sw_scan_topk");
-    } else {
-        sw_gdb* gdb = nullptr;
-        check(sw_group_db_create(g, f.residues.data(), f.offsets.data(), n, ids.data(), &gdb), "sw_group_db_create");
-        g_timing.upload_s = now_s() - t0;
-        t0 = now_s();
-        const int rc = sw_group_topk(g, gdb, qc.data(), ql, &sc, k, keys.data());
-        g_timing.scan_s = now_s() - t0;
-        sw_group_db_free(gdb);
-        check(rc, "sw_group_topk");
-    }
-    for (int64_t key : keys) {
-        if (key == INT64_MIN) break;  // fewer subjects than k
-        out.push_back(std::make_pair(static_cast<int>((int64_t{1} << 31) - 1 - (key & 0xffffffff)),
-                                     static_cast<int>(key >> 32)));
-    }
-    return out;
-}
-
-namespace {
-// smith_waterman_cuda_hits; sig (nullable): its _sig form (sw_scan_hits_sig);
-// n_pass (nullable, with sig): its _ranked form under max_evalue (sw_scan_hits_ranked).
-std::vector<sw_hit> hits_call(FASTAQuery& query, FASTADatabase& db, int k, std::vector<sw_sig>* sig, sw_calib* calib,
-                              int64_t* n_pass = nullptr, double max_evalue = 0) {
-    if (k < 1 || k > 4096) throw std::invalid_argument("the hit table needs 1 <= k <= 4096");
-    std::lock_guard<std::mutex> lock(g_mu);
-    // coordinates are those of the sequences as written: no '/' padding of
-    // the subjects or the query (it scores 0 under the reference's table, so
-    // the scores are smith_waterman_cuda_topk's under any scoring)
-    const Flat f = timed_flatten(db, true);
-    const int64_t n = static_cast<int64_t>(f.record_ids.size());
-    for (int id : f.record_ids)
-        if (id < 0) throw std::invalid_argument("the hit table needs record ids (a FASTA header per subject)");
-    const std::vector<uint8_t> qc = encode_query(query, false);
-    const sw_scoring sc = {g_sc.has_matrix ? g_sc.mat : nullptr, g_sc.go, g_sc.ge};
-    std::vector<int32_t> ids(f.record_ids.begin(), f.record_ids.end());
-    std::vector<sw_hit> out(static_cast<size_t>(k));
-    g_timing.gpus = 1;
-    double t0 = now_s();
-    sw_handle* h = handle();
-    g_timing.init_s = now_s() - t0;
-    t0 = now_s();
-    sw_db* sdb = nullptr;
-    check(sw_db_create(h, f.residues.data(), f.offsets.data(), n, ids.data(), &sdb), "sw_db_create");
-    g_timing.upload_s = now_s() - t0;
-    t0 = now_s();
-    int32_t nhits = 0;
-    if (sig) sig->assign(static_cast<size_t>(k), sw_sig{});
-    const int rc = n_pass ? sw_scan_hits_ranked(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, k, max_evalue,
-                                                out.data(), sig->data(), &nhits, n_pass, calib)
-                   : sig  ? sw_scan_hits_sig(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, k, out.data(),
-                                             sig->data(), &nhits, calib)
-                          : sw_scan_hits(h, sdb, qc.data(), static_cast<int32_t>(qc.size()), &sc, k, out.data(), &nhits);
-    g_timing.scan_s = now_s() - t0;
-    sw_db_free(sdb);
-    check(rc, n_pass ? "sw_scan_hits_ranked" : sig ? "sw_scan_hits_sig" : "sw_scan_hits");
-    out.resize(static_cast<size_t>(nhits));
-    if (sig) sig->resize(static_cast<size_t>(nhits));
-    return out;
-}
-}  // namespace
-
-std::vector<sw_hit> smith_waterman_cuda_hits(FASTAQuery& query, FASTADatabase& db, int k) {
-    return hits_call(query, db, k, nullptr, nullptr);
-}
-
-std::vector<sw_hit> smith_waterman_cuda_hits_sig(FASTAQuery& query, FASTADatabase& db, int k, std::vector<sw_sig>* sig,
-                                                 sw_calib* calib) {
-    if (!sig) throw std::invalid_argument("smith_waterman_cuda_hits_sig needs a vector for the significances");
-    return hits_call(query, db, k, sig, calib);
-}
-
-std::vector<sw_hit> smith_waterman_cuda_hits_ranked(FASTAQuery& query, FASTADatabase& db, int k, double max_evalue,
-                                                    std::vector<sw_sig>* sig, int64_t* n_pass, sw_calib* calib) {
-    if (!sig) throw std::invalid_argument("smith_waterman_cuda_hits_ranked needs a vector for the significances");
-    int64_t np = 0;
-    return hits_call(query, db, k, sig, calib, n_pass ? n_pass : &np, max_evalue);
-}
-
 bool sw_solver_read_queries(const std::string& path, std::vector<std::string>* names, std::vector<std::string>* seqs,
                             std::string* err) {
     auto bad = [&](const std::string& why) {
@@ -638,71 +654,121 @@ bool sw_solver_read_queries(const std::string& path, std::vector<std::string>* n
     return true;
 }
 
-namespace {
-// The shared front of the two batch calls: k, the database as written with
-// its record ids, the queries as written, concatenated; then `run` under the
-// set scoring.
-template <class Run>
-void batch_call(const std::vector<std::string>& seqs, FASTADatabase& db, int k, const char* what, Run run) {
-    if (k < 1 || k > 4096) throw std::invalid_argument("a batch of queries needs 1 <= k <= 4096");
+void sw_solver_set_scoring(const int8_t* matrix625, int gap_open, int gap_extend) {
+    if (gap_open < 1 || gap_open > 1000 || gap_extend < 1 || gap_extend > 1000)
+        throw std::invalid_argument("gap penalties must be in 1..1000");
+    if (matrix625)
+        for (int k = 0; k < 625; ++k)
+            if (matrix625[k] < -100 || matrix625[k] > 100)
+                throw std::invalid_argument("matrix entries must be in -100..100");
     std::lock_guard<std::mutex> lock(g_mu);
-    const Flat f = timed_flatten(db, true);
-    const int64_t n = static_cast<int64_t>(f.record_ids.size());
-    for (int id : f.record_ids)
-        if (id < 0) throw std::invalid_argument("a batch of queries needs record ids (a FASTA header per subject)");
-    std::vector<int64_t> qoffs(seqs.size() + 1, 0);
-    for (size_t q = 0; q < seqs.size(); ++q) qoffs[q + 1] = qoffs[q] + static_cast<int64_t>(seqs[q].size());
-    std::vector<uint8_t> qc(static_cast<size_t>(qoffs.back()));
-    for (size_t q = 0; q < seqs.size(); ++q)
-        check(sw_encode(seqs[q].data(), static_cast<int64_t>(seqs[q].size()), qc.data() + qoffs[q]), "sw_encode");
-    const sw_scoring sc = {g_sc.has_matrix ? g_sc.mat : nullptr, g_sc.go, g_sc.ge};
-    std::vector<int32_t> ids(f.record_ids.begin(), f.record_ids.end());
-    g_timing.gpus = 1;
-    double t0 = now_s();
-    sw_handle* h = handle();
-    g_timing.init_s = now_s() - t0;
-    t0 = now_s();
-    sw_db* sdb = nullptr;
-    check(sw_db_create(h, f.residues.data(), f.offsets.data(), n, ids.data(), &sdb), "sw_db_create");
-    g_timing.upload_s = now_s() - t0;
-    t0 = now_s();
-    const int rc = run(h, sdb, qc.data(), qoffs.data(), static_cast<int32_t>(seqs.size()), &sc);
-    g_timing.scan_s = now_s() - t0;
-    sw_db_free(sdb);
-    check(rc, what);
+    g_sc = SolverScoring{};
+    g_sc.custom = true;
+    g_sc.has_matrix = matrix625 != nullptr;
+    if (matrix625) std::memcpy(g_sc.mat, matrix625, 625);
+    g_sc.go = gap_open;
+    g_sc.ge = gap_extend;
+}
+
+void sw_solver_reset_scoring() {
+    std::lock_guard<std::mutex> lock(g_mu);
+    g_sc = SolverScoring{};
+}
+
+sw_search_result sw_solver_search(const std::string& db_path, const sw_search_request& rq) {
+    if (db_path.size() > 5 && db_path.compare(db_path.size() - 5, 5, ".swdb") == 0) return search(nullptr, db_path, rq);
+    const double t0 = now_s();
+    FASTADatabase fdb(db_path);
+    const double parse_s = now_s() - t0;
+    const double t1 = now_s();
+    sw_search_result r = search(&fdb, std::string(), rq);
+    r.parse_s = parse_s;
+    r.solve_s = now_s() - t1;  // a FASTA's: flatten, upload, scan, and the database freed again
+    return r;
+}
+
+void smith_waterman_cuda(FASTAQuery& query, FASTADatabase& db, std::vector<seqid_score>& result) {
+    const std::string q = query.get_buffer();
+    const sw_search_result r = search(&db, std::string(), request(&q, nullptr, nullptr, sw_search_request::SCORES, 0));
+    result.insert(result.end(), r.scores[0].begin(), r.scores[0].end());
+}
+
+// Scores equal smith_waterman_cuda's (golden-pinned), returned in file order;
+// SW_CHAR_COMPAT=1 scores with the _char path's own table instead
+// (SURVEY.md §8 f4, SW_MATRIX_BLOSUM50_CHAR).
+std::vector<seqid_score> smith_waterman_cuda_char(FASTAQuery& query, FASTADatabase& db) {
+    const std::string q = query.get_buffer();
+    const char* cc = std::getenv("SW_CHAR_COMPAT");
+    std::vector<seqid_score> out = search(&db, std::string(), request(&q, nullptr, nullptr, sw_search_request::SCORES, 0),
+                                          cc && cc[0] == '1' ? CharPath::TABLE : CharPath::ORDER).scores[0];
+    std::stable_sort(out.begin(), out.end(),
+                     [](const seqid_score& a, const seqid_score& b) { return a.first < b.first; });
+    return out;
+}
+
+std::vector<seqid_score> smith_waterman_cuda_topk(FASTAQuery& query, FASTADatabase& db, int k) {
+    if (k < 1) throw std::invalid_argument("top-k needs k >= 1");
+    const std::string q = query.get_buffer();
+    return search(&db, std::string(), request(&q, nullptr, nullptr, sw_search_request::TOPK, k)).scores[0];
+}
+
+std::vector<seqid_score> smith_waterman_cuda_pssm(const std::vector<int8_t>& rows, FASTADatabase& db, int k) {
+    if (k < 0) throw std::invalid_argument("top-k needs k >= 0");
+    if (rows.size() % 25 != 0) throw std::invalid_argument("a PSSM holds 25 entries per row");
+    const sw_search_request::Mode mode = k ? sw_search_request::TOPK : sw_search_request::SCORES;
+    return search(&db, std::string(), request(nullptr, nullptr, &rows, mode, k)).scores[0];
+}
+
+namespace {
+// The hit-table entry points: one query (seqs null) or a batch; `evalue` asks
+// for significances and calibrations, `ranked` for the E-value order as well.
+sw_search_result hits_search(const std::string* query, const std::vector<std::string>* seqs, FASTADatabase& db, int k,
+                             bool evalue, bool ranked, double max_evalue) {
+    sw_search_request rq = request(query, seqs, nullptr, sw_search_request::HITS, k);
+    rq.evalue = evalue;
+    rq.ranked = ranked;
+    rq.max_evalue = max_evalue;
+    return search(&db, std::string(), rq);
 }
 }  // namespace
 
+namespace {
+// The three one-query forms: sig null for the plain table; `ranked` for the E-value order.
+std::vector<sw_hit> query_hits(FASTAQuery& query, FASTADatabase& db, int k, bool ranked, double max_evalue,
+                               std::vector<sw_sig>* sig, int64_t* n_pass, sw_calib* calib) {
+    const std::string q = query.get_buffer();
+    sw_search_result r = hits_search(&q, nullptr, db, k, sig != nullptr, ranked, max_evalue);
+    if (sig) sig->swap(r.sigs[0]);
+    if (sig && calib) *calib = r.calibs[0];
+    if (ranked && n_pass) *n_pass = r.n_pass[0];
+    return r.rows[0];
+}
+}  // namespace
+
+std::vector<sw_hit> smith_waterman_cuda_hits(FASTAQuery& query, FASTADatabase& db, int k) {
+    return query_hits(query, db, k, false, 0, nullptr, nullptr, nullptr);
+}
+
+std::vector<sw_hit> smith_waterman_cuda_hits_sig(FASTAQuery& query, FASTADatabase& db, int k, std::vector<sw_sig>* sig,
+                                                 sw_calib* calib) {
+    if (!sig) throw std::invalid_argument("smith_waterman_cuda_hits_sig needs a vector for the significances");
+    return query_hits(query, db, k, false, 0, sig, nullptr, calib);
+}
+
+std::vector<sw_hit> smith_waterman_cuda_hits_ranked(FASTAQuery& query, FASTADatabase& db, int k, double max_evalue,
+                                                    std::vector<sw_sig>* sig, int64_t* n_pass, sw_calib* calib) {
+    if (!sig) throw std::invalid_argument("smith_waterman_cuda_hits_ranked needs a vector for the significances");
+    return query_hits(query, db, k, true, max_evalue, sig, n_pass, calib);
+}
+
 std::vector<std::vector<seqid_score>> smith_waterman_cuda_batch_topk(const std::vector<std::string>& seqs,
                                                                      FASTADatabase& db, int k) {
-    std::vector<int64_t> keys(seqs.size() * static_cast<size_t>(std::max(k, 0)));
-    batch_call(seqs, db, k, "sw_scan_batch_topk",
-               [&](sw_handle* h, sw_db* sdb, const uint8_t* qc, const int64_t* qoffs, int32_t nq, const sw_scoring* sc) {
-                   return sw_scan_batch_topk(h, sdb, qc, qoffs, nq, sc, k, keys.data());
-               });
-    std::vector<std::vector<seqid_score>> out(seqs.size());
-    for (size_t q = 0; q < seqs.size(); ++q)
-        for (int i = 0; i < k; ++i) {
-            const int64_t key = keys[q * static_cast<size_t>(k) + i];
-            if (key == INT64_MIN) break;  // fewer subjects than k
-            out[q].push_back(std::make_pair(static_cast<int>((int64_t{1} << 31) - 1 - (key & 0xffffffff)),
-                                            static_cast<int>(key >> 32)));
-        }
-    return out;
+    return search(&db, std::string(), request(nullptr, &seqs, nullptr, sw_search_request::TOPK, k)).scores;
 }
 
 std::vector<std::vector<sw_hit>> smith_waterman_cuda_batch_hits(const std::vector<std::string>& seqs,
                                                                 FASTADatabase& db, int k) {
-    std::vector<sw_hit> rows(seqs.size() * static_cast<size_t>(std::max(k, 0)));
-    int32_t nhits = 0;
-    batch_call(seqs, db, k, "sw_scan_batch_hits",
-               [&](sw_handle* h, sw_db* sdb, const uint8_t* qc, const int64_t* qoffs, int32_t nq, const sw_scoring* sc) {
-                   return sw_scan_batch_hits(h, sdb, qc, qoffs, nq, sc, k, rows.data(), &nhits);
-               });
-    std::vector<std::vector<sw_hit>> out(seqs.size());
-    for (size_t q = 0; q < seqs.size(); ++q)
-        out[q].assign(rows.begin() + static_cast<int64_t>(q) * k, rows.begin() + static_cast<int64_t>(q) * k + nhits);
-    return out;
+    return hits_search(nullptr, &seqs, db, k, false, false, 0).rows;
 }
 
 std::vector<std::vector<sw_hit>> smith_waterman_cuda_batch_hits_sig(const std::vector<std::string>& seqs,
@@ -710,23 +776,10 @@ std::vector<std::vector<sw_hit>> smith_waterman_cuda_batch_hits_sig(const std::v
                                                                     std::vector<std::vector<sw_sig>>* sig,
                                                                     std::vector<sw_calib>* calib) {
     if (!sig || !calib) throw std::invalid_argument("smith_waterman_cuda_batch_hits_sig needs its two output vectors");
-    const size_t kk = static_cast<size_t>(std::max(k, 0));
-    std::vector<sw_hit> rows(seqs.size() * kk);
-    std::vector<sw_sig> sigs(seqs.size() * kk);
-    calib->assign(seqs.size(), sw_calib{});
-    int32_t nhits = 0;
-    batch_call(seqs, db, k, "sw_scan_batch_hits_sig",
-               [&](sw_handle* h, sw_db* sdb, const uint8_t* qc, const int64_t* qoffs, int32_t nq, const sw_scoring* sc) {
-                   return sw_scan_batch_hits_sig(h, sdb, qc, qoffs, nq, sc, k, rows.data(), sigs.data(), &nhits,
-                                                 calib->data());
-               });
-    std::vector<std::vector<sw_hit>> out(seqs.size());
-    sig->assign(seqs.size(), std::vector<sw_sig>());
-    for (size_t q = 0; q < seqs.size(); ++q) {
-        out[q].assign(rows.begin() + static_cast<int64_t>(q) * k, rows.begin() + static_cast<int64_t>(q) * k + nhits);
-        (*sig)[q].assign(sigs.begin() + static_cast<int64_t>(q) * k, sigs.begin() + static_cast<int64_t>(q) * k + nhits);
-    }
-    return out;
+    sw_search_result r = hits_search(nullptr, &seqs, db, k, true, false, 0);
+    sig->swap(r.sigs);
+    calib->swap(r.calibs);
+    return r.rows;
 }
 
 std::vector<std::vector<sw_hit>> smith_waterman_cuda_batch_hits_ranked(const std::vector<std::string>& seqs,
@@ -736,52 +789,26 @@ std::vector<std::vector<sw_hit>> smith_waterman_cuda_batch_hits_ranked(const std
                                                                        std::vector<sw_calib>* calib) {
     if (!sig || !n_pass || !calib)
         throw std::invalid_argument("smith_waterman_cuda_batch_hits_ranked needs its three output vectors");
-    const size_t kk = static_cast<size_t>(std::max(k, 0));
-    std::vector<sw_hit> rows(seqs.size() * kk);
-    std::vector<sw_sig> sigs(seqs.size() * kk);
-    std::vector<int32_t> nhits(seqs.size(), 0);
-    calib->assign(seqs.size(), sw_calib{});
-    n_pass->assign(seqs.size(), 0);
-    batch_call(seqs, db, k, "sw_scan_batch_hits_ranked",
-               [&](sw_handle* h, sw_db* sdb, const uint8_t* qc, const int64_t* qoffs, int32_t nq, const sw_scoring* sc) {
-                   return sw_scan_batch_hits_ranked(h, sdb, qc, qoffs, nq, sc, k, max_evalue, 0, rows.data(), sigs.data(),
-                                                    nhits.data(), n_pass->data(), calib->data());
-               });
-    std::vector<std::vector<sw_hit>> out(seqs.size());
-    sig->assign(seqs.size(), std::vector<sw_sig>());
-    for (size_t q = 0; q < seqs.size(); ++q) {
-        out[q].assign(rows.begin() + static_cast<int64_t>(q) * k, rows.begin() + static_cast<int64_t>(q) * k + nhits[q]);
-        (*sig)[q].assign(sigs.begin() + static_cast<int64_t>(q) * k, sigs.begin() + static_cast<int64_t>(q) * k + nhits[q]);
-    }
-    return out;
-}
-
-void smith_waterman_cuda(FASTAQuery& query, FASTADatabase& db, std::vector<seqid_score>& result) {
-    std::lock_guard<std::mutex> lock(g_mu);  // the reference is not re-entrant either
-    const Flat f = timed_flatten(db, g_sc.custom);
-    const std::vector<int32_t> scores = score_all(query, f);
-    for (size_t k = 0; k < scores.size(); ++k) result.push_back(std::make_pair(f.record_ids[k], scores[k]));
+    sw_search_result r = hits_search(nullptr, &seqs, db, k, true, true, max_evalue);
+    sig->swap(r.sigs);
+    n_pass->swap(r.n_pass);
+    calib->swap(r.calibs);
+    return r.rows;
 }
 
 void sw_save_fasta_db(FASTADatabase& fdb, const std::string& path) {
     std::lock_guard<std::mutex> lock(g_mu);
-    const Flat f = flatten(fdb, true);  // as written; main's METRICS restore the padded sizes
-    const int64_t n = static_cast<int64_t>(f.record_ids.size());
-    std::vector<int32_t> ids(f.record_ids.begin(), f.record_ids.end());
-    sw_db* db = nullptr;
-    check(sw_db_create(handle(), f.residues.data(), f.offsets.data(), n, n ? ids.data() : nullptr, &db),
+    const Subjects s(fdb, true);  // as written; a search of the file restores the padded sizes for METRICS
+    sw_db* made = nullptr;
+    check(sw_db_create(handle(), s.residues.data(), s.offsets.data(), s.n(), s.n() ? s.ids.data() : nullptr, &made),
           "sw_db_create");
-    const int rc = sw_db_save(db, path.c_str());
-    sw_db_free(db);
-    check(rc, "sw_db_save");
+    const sw_db_ptr db(made);
+    check(sw_db_save(db.get(), path.c_str()), "sw_db_save");
 }
 
 void sw_solver_set_gpus(int n) {
     std::lock_guard<std::mutex> lock(g_mu);
-    if (n != g_gpus && g_group) {
-        sw_group_destroy(g_group);
-        g_group = nullptr;
-    }
+    if (n != g_gpus) g_group.reset();
     g_gpus = n;
 }
 
@@ -791,18 +818,3 @@ sw_group* sw_solver_group() {
 }
 
 sw_solver_timing sw_solver_last_timing() { return g_timing; }
-
-// Scores equal smith_waterman_cuda's (golden-pinned), returned in file order;
-// SW_CHAR_COMPAT=1 scores with the _char path's own table instead
-// (SURVEY.md §8 f4, SW_MATRIX_BLOSUM50_CHAR).
-std::vector<seqid_score> smith_waterman_cuda_char(FASTAQuery& query, FASTADatabase& db) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    const Flat f = timed_flatten(db, false);
-    const char* cc = std::getenv("SW_CHAR_COMPAT");
-    const std::vector<int32_t> scores = score_all(query, f, cc && cc[0] == '1');
-    std::vector<seqid_score> out(scores.size());
-    for (size_t k = 0; k < scores.size(); ++k) out[k] = std::make_pair(f.record_ids[k], scores[k]);
-    std::stable_sort(out.begin(), out.end(),
-                     [](const seqid_score& a, const seqid_score& b) { return a.first < b.first; });
-    return out;
-}

@@ -155,4 +155,37 @@ bool sw_solver_read_pssm(const std::string& path, std::vector<int8_t>* rows, std
 std::vector<seqid_score> smith_waterman_cuda_pssm(const std::vector<int8_t>& rows, FASTADatabase& db,
                                                   int k /* 0 = all, in the reference's report order */);
 
+/* The one search behind every function above, and `main`'s only one: what is
+ * searched for (exactly one of query, queries and pssm is non-null), which
+ * result is wanted, and the database by path, a FASTA file or a .swdb file
+ * (sw_save_fasta_db).  Per query, in the order given: scores (SCORES: every
+ * subject in the reference's report order; TOPK: the k best) or rows (HITS),
+ * with sigs and calibs under `evalue`, in E-value order with n_pass under
+ * `ranked` (needs evalue; max_evalue as smith_waterman_cuda_hits_ranked's).
+ * A .swdb file is scanned on one GPU whatever sw_solver_set_gpus says.
+ * Throws what the functions above throw. */
+struct sw_search_request {
+    const std::string* query;                /* the residues as written */
+    const std::vector<std::string>* queries; /* a batch: HITS or TOPK, k in 1..4096 */
+    const std::vector<int8_t>* pssm;         /* [positions][25]: SCORES or TOPK */
+    enum Mode { SCORES, TOPK, HITS } mode;
+    int k;
+    bool evalue, ranked;
+    double max_evalue;
+};
+struct sw_search_result {
+    std::vector<std::vector<seqid_score> > scores;
+    std::vector<std::vector<sw_hit> > rows;
+    std::vector<std::vector<sw_sig> > sigs;
+    std::vector<sw_calib> calibs;
+    std::vector<int64_t> n_pass;
+    /* main's METRICS: the FASTA parser's counts (subjects padded to TILE_SIZE),
+     * the same for a file; the wall time of parsing a FASTA (0 for a file) and
+     * of the search after it (a FASTA's: flatten, upload, scan and freeing the
+     * database; a file's: the scan once it is loaded) */
+    int64_t num_subjects = 0, padded_residues = 0;
+    double parse_s = 0, solve_s = 0;
+};
+sw_search_result sw_solver_search(const std::string& db_path, const sw_search_request& rq);
+
 #endif /* SW_SOLVER_EXT_H */

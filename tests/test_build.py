@@ -18,7 +18,7 @@ CSRC = os.path.join(REPO, "ece1782-smith-waterman-cuda_amd", "csrc")
 INCDIRS = (CSRC, os.path.join(REPO, "include"))
 INCLUDE_RE = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
 # translation units the Makefile compiles, and the object each one makes
-HOST_TUS = ("main.cpp", "swsolver.cpp", "sw_tests.cpp")
+HOST_TUS = ("main.cpp", "sw_cli.cpp", "swsolver.cpp", "sw_tests.cpp")
 
 
 def _obj(src):

@@ -58,7 +58,7 @@ def test_no_environment_read_on_the_scan_path():
     # Makefile's HOSTOBJS: the CLI and the C++ drop-in pick their devices from
     # SW_DEVICE & co.)
     programs = re.search(r"^HOSTOBJS\s*:=\s*(.+)$", open(os.path.join(CSRC, "Makefile")).read(), re.M).group(1).split()
-    assert sorted(programs) == ["main", "sw_tests", "swsolver"]
+    assert sorted(programs) == ["main", "sw_cli", "sw_tests", "swsolver"]
     sources = sorted(s for s in os.listdir(CSRC)
                      if s.endswith((".cpp", ".hip", ".h")) and s.rsplit(".", 1)[0] not in programs)
     assert len(sources) >= 30 and "sw_hits.hip" in sources and "sw_plan.cpp" in sources
