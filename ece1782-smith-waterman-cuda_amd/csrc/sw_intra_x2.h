@@ -91,8 +91,16 @@ struct IntraCell {
     }
     static __device__ __forceinline__ uint32_t pair_of(int v) { const uint32_t b = f16_bits(v); return b | (b << 16); }
     static __device__ __forceinline__ uint32_t convert(uint32_t w, int b0, int b1) { return f16x2_of(w, b0, b1); }
-    static __device__ __forceinline__ int lo(V x) { return static_cast<int>(static_cast<float>(x.x)); }
-    static __device__ __forceinline__ int hi(V x) { return static_cast<int>(static_cast<float>(x.y)); }
+    // A subject past the guard keeps computing, and past 65504 its maximum is
+    // +inf (a score of 110,000 under +-100 entries): 65536 then, above every
+    // sat_limit, so that it is flagged (an inf or NaN converted as it stands
+    // came out negative once the offset was removed, and was not).
+    static __device__ __forceinline__ int to_int(_Float16 h) {
+        const float f = static_cast<float>(h);
+        return f < 65536.f ? static_cast<int>(f) : 65536;
+    }
+    static __device__ __forceinline__ int lo(V x) { return to_int(x.x); }
+    static __device__ __forceinline__ int hi(V x) { return to_int(x.y); }
     template <int RI>
     static __device__ __forceinline__ bool flag(const IntraArgs& a, int b) { return b >= a.sat_limit; }
 };

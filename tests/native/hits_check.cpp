@@ -6,7 +6,9 @@
 //             swo_align_linear / swo_align_affine): spans, ops length,
 //             identities and positives by replaying the ops over the two
 //             sequences, runs of I or of D for gap_opens; and three injected
-//             faults, each of which some pair must notice;
+//             faults, each of which some pair must notice; once over 2 to 4
+//             codes (tie-heavy) and once over all 25 codes under asymmetric
+//             matrices at the scoring envelope's edges;
 //   location  swpack::locate + swk::hit_residue_at against the bytes
 //             fill_block / fill_long write: every subject's residues are
 //             recovered from its location;
@@ -98,6 +100,44 @@ static sw_hit carried_row(const Pair& p, const Scoring& sc) {
     return r;
 }
 
+// Every pair under every scoring: the carried row equals the oracle's; the
+// counts printed under `tag` are what tests/test_hits_cpu.py asserts.
+static void run_rules(const char* tag, const std::vector<Scoring>& scorings, const std::vector<Pair>& pairs, int at_least) {
+    int total = 0, gapped = 0, adjacent = 0, zero = 0, id_over_pos = 0, pos_over_id = 0, big = 0, caught[4] = {};
+    for (const Scoring& sc : scorings)
+        for (const Pair& p : pairs) {
+            std::string ops;
+            const sw_hit want = oracle_row(p, sc, &ops);
+            const sw_hit got = carried_row<swhits::kFaultNone>(p, sc);
+            ++total;
+            gapped += want.gaps > 0;
+            adjacent += ops.find("ID") != std::string::npos || ops.find("DI") != std::string::npos;
+            zero += want.score == 0;
+            id_over_pos += want.identities > want.positives;
+            pos_over_id += want.positives > want.identities;
+            big += want.score > 32767;
+            CHECK(same_row(got, want),
+                  "%s pair %d: carried %d [%d,%d]x[%d,%d] len %d id %d pos %d opens %d gaps %d, oracle %d [%d,%d]x[%d,%d] "
+                  "len %d id %d pos %d opens %d gaps %d (%s)",
+                  sc.name, total, got.score, got.q_begin, got.q_end, got.s_begin, got.s_end, got.length, got.identities,
+                  got.positives, got.gap_opens, got.gaps, want.score, want.q_begin, want.q_end, want.s_begin, want.s_end,
+                  want.length, want.identities, want.positives, want.gap_opens, want.gaps, ops.c_str());
+            caught[1] += !same_row(carried_row<swhits::kFaultLastOp>(p, sc), want);
+            caught[2] += !same_row(carried_row<swhits::kFaultTieBegin>(p, sc), want);
+            caught[3] += !same_row(carried_row<swhits::kFaultPositives>(p, sc), want);
+        }
+    CHECK(total >= at_least, "only %d pairs", total);
+    CHECK(3 * gapped >= total, "only %d of %d alignments contain a gap", gapped, total);
+    CHECK(adjacent > 0, "no alignment has adjacent I and D runs");
+    CHECK(caught[1] > 0, "no pair notices a last op dropped at a source change");
+    CHECK(caught[2] > 0, "no pair notices a begin cell taken from the losing source of a tie");
+    CHECK(caught[3] > 0, "no pair notices positives counted on entries >= 0");
+    std::printf("%s: %d pairs, %d gapped, %d adjacent-runs, %d score-0, faults caught %d %d %d\n", tag, total, gapped,
+                adjacent, zero, caught[1], caught[2], caught[3]);
+    std::printf("%s-counts: %d identities-over-positives, %d positives-over-identities, %d over-16-bits\n", tag, id_over_pos,
+                pos_over_id, big);
+}
+
 static void check_rules() {
     std::mt19937 rng(20261);
     auto rnd = [&](int lo, int hi) { return lo + static_cast<int>(rng() % static_cast<unsigned>(hi - lo + 1)); };
@@ -147,34 +187,78 @@ static void check_rules() {
         }
         pairs.push_back(p);
     }
-    int total = 0, gapped = 0, adjacent = 0, zero = 0, caught[4] = {};
-    for (const Scoring& sc : scorings)
-        for (const Pair& p : pairs) {
-            std::string ops;
-            const sw_hit want = oracle_row(p, sc, &ops);
-            const sw_hit got = carried_row<swhits::kFaultNone>(p, sc);
-            ++total;
-            gapped += want.gaps > 0;
-            adjacent += ops.find("ID") != std::string::npos || ops.find("DI") != std::string::npos;
-            zero += want.score == 0;
-            CHECK(same_row(got, want),
-                  "%s pair %d: carried %d [%d,%d]x[%d,%d] len %d id %d pos %d opens %d gaps %d, oracle %d [%d,%d]x[%d,%d] "
-                  "len %d id %d pos %d opens %d gaps %d (%s)",
-                  sc.name, total, got.score, got.q_begin, got.q_end, got.s_begin, got.s_end, got.length, got.identities,
-                  got.positives, got.gap_opens, got.gaps, want.score, want.q_begin, want.q_end, want.s_begin, want.s_end,
-                  want.length, want.identities, want.positives, want.gap_opens, want.gaps, ops.c_str());
-            caught[1] += !same_row(carried_row<swhits::kFaultLastOp>(p, sc), want);
-            caught[2] += !same_row(carried_row<swhits::kFaultTieBegin>(p, sc), want);
-            caught[3] += !same_row(carried_row<swhits::kFaultPositives>(p, sc), want);
+    run_rules("rules", scorings, pairs, 2000);
+}
+
+// The same pass over all 25 codes (B, J, Z, X and * included) under matrices
+// that are not symmetric: entries -12..12 with a positive diagonal (asym), the
+// same with three diagonal entries <= 0 (idneg: identities that are not
+// positives) and entries of +-100 (pm100); gaps from 1 to 1000 and an open
+// below the extend; sequences up to 200 residues.  A rules error at the
+// envelope's edges shows here, on the CPU; tests/test_gpu_hits_envelope.py is
+// left to find the kernel's own (profile, hand-overs, reduction).
+static void check_rules25() {
+    std::mt19937 rng(20262);
+    auto rnd = [&](int lo, int hi) { return lo + static_cast<int>(rng() % static_cast<unsigned>(hi - lo + 1)); };
+    auto asymmetric = [](const std::vector<int8_t>& m) {
+        int n = 0;
+        for (int a = 0; a < 25; ++a)
+            for (int b = 0; b < a; ++b) n += m[25 * a + b] != m[25 * b + a];
+        return n;
+    };
+    std::vector<int8_t> asym(625), pm100(625);
+    for (auto& v : asym) v = static_cast<int8_t>(rnd(-12, 12));
+    for (int a = 0; a < 25; ++a) asym[26 * a] = static_cast<int8_t>(rnd(3, 13));
+    std::vector<int8_t> idneg = asym;
+    idneg[26 * 4] = 0;
+    idneg[26 * 21] = -2;
+    idneg[26 * 23] = 0;
+    for (auto& v : pm100) v = rnd(0, 9) < 3 ? 100 : -100;
+    for (int a = 0; a < 24; ++a) pm100[26 * a] = 100;
+    pm100[26 * 24] = -100;
+    CHECK(asymmetric(asym) > 100 && asymmetric(idneg) > 100 && asymmetric(pm100) > 50,
+          "a 25-code matrix is (nearly) symmetric: %d %d %d", asymmetric(asym), asymmetric(idneg), asymmetric(pm100));
+    std::vector<Scoring> scorings;
+    scorings.push_back({"asym-12-1", asym, 12, 1});
+    scorings.push_back({"asym-2-2", asym, 2, 2});
+    scorings.push_back({"asym-1-4-open-below-extend", asym, 1, 4});
+    scorings.push_back({"idneg-11-1", idneg, 11, 1});
+    scorings.push_back({"pm100-1000-1000", pm100, 1000, 1000});
+    scorings.push_back({"pm100-3-1", pm100, 3, 1});
+    constexpr int kPairs = 260;
+    std::vector<Pair> pairs;
+    bool seen_q[25] = {}, seen_s[25] = {};
+    for (int k = 0; k < kPairs; ++k) {
+        Pair p;
+        p.q.resize(static_cast<size_t>(k % 5 == 0 ? rnd(150, 200) : rnd(1, 200)));
+        for (auto& c : p.q) c = static_cast<uint8_t>(rnd(0, 24));
+        if (k % 3 == 0) {  // unrelated
+            p.s.resize(static_cast<size_t>(rnd(1, 200)));
+            for (auto& c : p.s) c = static_cast<uint8_t>(rnd(0, 24));
+        } else {  // a copy with deletions, insertions and substitutions
+            p.s = p.q;
+            for (int e = rnd(1, 4); e > 0 && !p.s.empty(); --e) {
+                const size_t at = static_cast<size_t>(rnd(0, static_cast<int>(p.s.size()) - 1));
+                const int L = rnd(1, 5);
+                if (rnd(0, 1)) {
+                    p.s.erase(p.s.begin() + at, p.s.begin() + std::min(p.s.size(), at + L));
+                } else {
+                    std::vector<uint8_t> ins(static_cast<size_t>(L));
+                    for (auto& c : ins) c = static_cast<uint8_t>(rnd(0, 24));
+                    p.s.insert(p.s.begin() + at, ins.begin(), ins.end());
+                }
+            }
+            for (int e = rnd(0, 6); e > 0 && !p.s.empty(); --e)
+                p.s[static_cast<size_t>(rnd(0, static_cast<int>(p.s.size()) - 1))] = static_cast<uint8_t>(rnd(0, 24));
+            if (p.s.empty()) p.s.push_back(24);
+            if (p.s.size() > 200) p.s.resize(200);
         }
-    CHECK(total >= 2000, "only %d pairs", total);
-    CHECK(3 * gapped >= total, "only %d of %d alignments contain a gap", gapped, total);
-    CHECK(adjacent > 0, "no alignment has adjacent I and D runs");
-    CHECK(caught[1] > 0, "no pair notices a last op dropped at a source change");
-    CHECK(caught[2] > 0, "no pair notices a begin cell taken from the losing source of a tie");
-    CHECK(caught[3] > 0, "no pair notices positives counted on entries >= 0");
-    std::printf("rules: %d pairs, %d gapped, %d adjacent-runs, %d score-0, faults caught %d %d %d\n", total, gapped,
-                adjacent, zero, caught[1], caught[2], caught[3]);
+        for (const uint8_t c : p.q) seen_q[c] = true;
+        for (const uint8_t c : p.s) seen_s[c] = true;
+        pairs.push_back(p);
+    }
+    for (int c = 0; c < 25; ++c) CHECK(seen_q[c] && seen_s[c], "code %d is in no query or in no subject", c);
+    run_rules("rules25", scorings, pairs, 1500);
 }
 
 // ---- location ---------------------------------------------------------------
@@ -326,6 +410,7 @@ static void check_align_groups() {
 
 int main() {
     check_rules();
+    check_rules25();
     for (int64_t n : {0, 1, 63, 64, 65, 129}) {
         check_location(n, 0, "all-long");
         check_location(n, 16, "t16");

@@ -32,6 +32,7 @@ import numpy as np
 import pytest
 
 from conftest import path_score
+from hits_envelope_support import build_matrices
 
 pytestmark = pytest.mark.gpu
 
@@ -39,28 +40,7 @@ A, R = 0, 1  # residue codes of 'A' and 'R'
 
 
 # ---- the scorings -----------------------------------------------------------
-def build_matrices(sw):
-    rng = np.random.default_rng(2024)
-    asym = rng.integers(-12, 13, size=(25, 25))
-    np.fill_diagonal(asym, rng.integers(3, 14, size=25))
-    one = np.full((25, 25), -5)
-    one[A, R] = 5
-    d100 = rng.integers(-100, 0, size=(25, 25))
-    d100[3, 17], d100[17, 3] = -100, -1
-    np.fill_diagonal(d100, 100)
-    nonpos = rng.integers(-12, 1, size=(25, 25))
-    nonpos[5, 5] = nonpos[2, 9] = 0
-    pm100 = np.where(rng.random((25, 25)) < 0.3, 100, -100)
-    np.fill_diagonal(pm100, 100)
-    pm100[24, 24] = -100
-    out = {"asym": asym, "one": one, "d100": d100, "nonpos": nonpos, "pm100": pm100,
-           "b50": sw.capi.builtin_matrix(0), "b62": sw.capi.builtin_matrix(1)}
-    out = {k: np.ascontiguousarray(v, dtype=np.int8) for k, v in out.items()}
-    for k in ("asym", "one", "d100", "nonpos", "pm100"):
-        assert (out[k] != out[k].T).any()
-    assert out["nonpos"].max() == 0 and out["d100"].max() == 100 and out["d100"].min() == -100
-    assert out["b62"].max() == 11 and out["b50"].max() == 15
-    return out
+# build_matrices(sw): tests/hits_envelope_support.py (the hit table's envelope tests share the matrices)
 
 
 # name: (matrix, open, extend, gap model of the kernels that run, fits 16 bits

@@ -2,8 +2,9 @@
 carried-tuple rules the kernel runs per cell (csrc/sw_hits_rules.h) as a
 scalar pass and compares every field with the row the oracle's traceback
 (oracle/sw_oracle.c swo_align_linear / swo_align_affine) implies, on random
-and tie-heavy pairs over 2 to 4 codes under six scorings; injects three
-faults that each must be noticed; recovers every subject's residues from its
+and tie-heavy pairs over 2 to 4 codes under six scorings, and on pairs over
+all 25 codes under six asymmetric scorings at the envelope's edges; injects
+three faults that each must be noticed; recovers every subject's residues from its
 location (swpack::locate + swk::hit_residue_at) in the bytes the packer
 writes; and checks the scratch size and the grouping of hits, the hit
 table's and sw_align's.  The CLI's
@@ -53,6 +54,25 @@ def test_carried_tuples_equal_the_oracles_traceback(hits_check):
     # a last op dropped at a source change, a begin cell from the losing source
     # of a tie, positives counted on entries >= 0: each changes some row
     assert f1 > 0 and f2 > 0 and f3 > 0
+
+
+@needs_hipcc
+def test_carried_tuples_over_all_25_codes(hits_check):
+    """The same pass over all 25 codes, sequences up to 200 residues, under
+    matrices that are not symmetric (checked natively): entries to +-100, gaps
+    of 1 to 1000, an open below the extend, diagonal entries <= 0.  The three
+    faults are noticed on these pairs alone."""
+    m = re.search(r"rules25: (\d+) pairs, (\d+) gapped, (\d+) adjacent-runs, (\d+) score-0, faults caught (\d+) (\d+) (\d+)",
+                  hits_check)
+    assert m, hits_check
+    pairs, gapped, adjacent, zero, f1, f2, f3 = map(int, m.groups())
+    assert pairs >= 1500 and 3 * gapped >= pairs and adjacent > 0
+    assert f1 > 0 and f2 > 0 and f3 > 0
+    m = re.search(r"rules25-counts: (\d+) identities-over-positives, (\d+) positives-over-identities, (\d+) over-16-bits",
+                  hits_check)
+    assert m, hits_check
+    id_over_pos, pos_over_id, big = map(int, m.groups())
+    assert id_over_pos >= 10 and pos_over_id >= 10 and big == 0  # (200 x 100 < 2^15: the GPU test has the large scores)
 
 
 @needs_hipcc
