@@ -39,6 +39,8 @@ EXPORTED = (
     "sw_scan_hits_sig", "sw_scan_batch_hits_sig", "sw_scan_pssm_topk_calib",
     "sw_sig_rank_table", "sw_sig_rank_min", "sw_sig_topk_device",
     "sw_scan_hits_ranked", "sw_scan_batch_hits_ranked", "sw_scan_pssm_topk_ranked",
+    "sw_pssm_rows", "sw_msa_pssm", "sw_profile_counts", "sw_profile_counts_msa", "sw_matrix_lambda",
+    "sw_pssm_from_counts", "sw_pssm_refine", "sw_search_iter",
     "sw_db_save", "sw_db_load", "sw_db_subjects", "sw_db_create_synthetic", "sw_synth_tables",
     "sw_synth_lengths", "sw_group_create", "sw_group_destroy", "sw_group_info", "sw_group_handle",
     "sw_group_db_create", "sw_group_db_free", "sw_group_db_shard", "sw_group_scan", "sw_group_topk",
@@ -108,6 +110,22 @@ class Calib(ctypes.Structure):
         c = Calib()
         ctypes.memmove(ctypes.byref(c), ctypes.byref(self), ctypes.sizeof(Calib))
         return c
+
+
+# Iterated profile search (include/sw_amd.h SW_MSA_*, SW_PROFILE_*): the bytes
+# of a query-anchored row that are not residues, the counted codes, the fixed
+# point of the row weights and the most hits a profile is built from.
+MSA_GAP = 25
+MSA_NONE = 26
+PROFILE_CODES = 20
+PROFILE_ONE = 1 << 30
+PROFILE_MAX_HITS = 4096
+
+
+class IterRound(ctypes.Structure):
+    """sw_iter_round (include/sw_amd.h): one round of sw_search_iter."""
+    _fields_ = [("included", ctypes.c_int32), ("added", ctypes.c_int32), ("dropped", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("calib", Calib)]
 
 
 class Sig(ctypes.Structure):
@@ -257,6 +275,21 @@ def lib():
                                                      i32p, i64p, ctypes.POINTER(Calib)]),
         "sw_scan_pssm_topk_ranked": (ctypes.c_int, [vp, vp, vp, i32, i32, i32, f64, i32p, i32p,
                                                     ctypes.POINTER(Sig), i32p, i64p, ctypes.POINTER(Calib)]),
+        "sw_pssm_rows": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int8)]),
+        "sw_msa_pssm": (ctypes.c_int, [vp, vp, vp, i32, i32, u8p, i32p, i32, u8p, ctypes.POINTER(Alignment)]),
+        "sw_profile_counts": (ctypes.c_int, [vp, vp, vp, i32, i32, u8p, i32p, i32, ctypes.POINTER(ctypes.c_uint32),
+                                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "sw_profile_counts_msa": (ctypes.c_int, [vp, u8p, i32, i32, ctypes.POINTER(ctypes.c_uint32),
+                                                 ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "sw_matrix_lambda": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int8), ctypes.POINTER(ctypes.c_double)]),
+        "sw_pssm_from_counts": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), i32,
+                                               ctypes.POINTER(ctypes.c_int8), ctypes.POINTER(ctypes.c_int8), f64,
+                                               ctypes.POINTER(ctypes.c_int8)]),
+        "sw_pssm_refine": (ctypes.c_int, [vp, vp, vp, i32, i32, u8p, ctypes.POINTER(ctypes.c_int8), f64, i32p, i32,
+                                          ctypes.POINTER(vp)]),
+        "sw_search_iter": (ctypes.c_int, [vp, vp, u8p, i32, ctypes.POINTER(Scoring), i32, f64, i32, f64, i32, f64,
+                                          i32p, i32p, ctypes.POINTER(Sig), i32p, i64p, ctypes.POINTER(Calib),
+                                          ctypes.POINTER(IterRound), i32p, i32p, ctypes.POINTER(vp)]),
         "sw_pssm_create": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int8), i32, ctypes.POINTER(vp)]),
         "sw_pssm_free": (ctypes.c_int, [vp]),
         "sw_pssm_length": (ctypes.c_int, [vp, i32p]),
@@ -473,8 +506,12 @@ class Pssm:
     rows is [qlen][25] int8, rows[i][c] = score of subject code c at query
     position i.  Takes the place of a query in Database.scan_pssm & co."""
 
-    def __init__(self, handle, rows):
+    def __init__(self, handle, rows, _adopt=None):
         self.handle = handle
+        if _adopt is not None:  # a sw_pssm the library created (refine_pssm, search_iter)
+            self._p = _adopt
+            handle._dbs.add(self)
+            return
         r = np.asarray(rows)
         if r.size and (r.ndim != 2 or r.shape[1] != SW_ALPHABET):
             raise SWError("a PSSM is a [qlen][%d] table" % SW_ALPHABET)
@@ -495,6 +532,12 @@ class Pssm:
         n = ctypes.c_int32()
         _check(lib().sw_pssm_length(self._p, ctypes.byref(n)))
         return n.value
+
+    def rows(self):
+        """The [qlen][25] int8 table (sw_pssm_rows)."""
+        out = np.zeros((len(self), SW_ALPHABET), dtype=np.int8)
+        _check(lib().sw_pssm_rows(self._p, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int8))))
+        return out
 
     def close(self):
         if self._p:
@@ -858,6 +901,90 @@ class Database:
                                    idv.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n, out, buf, stride))
         return self._alignments(out, n, buf, stride, ops_stride is not None or not ops)
 
+    # ---- iterated profile search (include/sw_amd.h) ----
+    @staticmethod
+    def _master(pssm, master):
+        if master is None:
+            return None, None
+        m, mp = _u8(master)
+        if len(m) != len(pssm):
+            raise SWError("the master sequence has the PSSM's length")
+        return m, mp
+
+    def msa_pssm(self, pssm, ids, master=None, gap=2, gap_extend=None):
+        """The query-anchored rows of these hits against a Pssm (sw_msa_pssm):
+        (uint8 [n + 1][qlen], alignments as align_pssm's without ops)."""
+        idv = np.ascontiguousarray(ids, dtype=np.int32)
+        n = len(idv)
+        m, mp = self._master(pssm, master)
+        out = np.zeros((n + 1, len(pssm)), dtype=np.uint8)
+        al = (Alignment * max(n, 1))()
+        _check(lib().sw_msa_pssm(self.handle.ptr, self._d, pssm.ptr, gap, gap if gap_extend is None else gap_extend,
+                                 mp, idv.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n,
+                                 out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), al))
+        return out, self._alignments(al, n, None, 0, True)
+
+    def profile_counts(self, pssm, ids, master=None, gap=2, gap_extend=None):
+        """The integer profile tables of these hits' rows, built on the device
+        (sw_profile_counts): (cnt uint32 [qlen][20], weight uint64 [n + 1],
+        wsum uint64 [qlen][20])."""
+        idv = np.ascontiguousarray(ids, dtype=np.int32)
+        n = len(idv)
+        m, mp = self._master(pssm, master)
+        cnt = np.zeros((len(pssm), PROFILE_CODES), dtype=np.uint32)
+        weight = np.zeros(n + 1, dtype=np.uint64)
+        wsum = np.zeros((len(pssm), PROFILE_CODES), dtype=np.uint64)
+        _check(lib().sw_profile_counts(self.handle.ptr, self._d, pssm.ptr, gap, gap if gap_extend is None else gap_extend,
+                                       mp, idv.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n,
+                                       cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                       weight.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                       wsum.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return cnt, weight, wsum
+
+    def refine_pssm(self, pssm, ids, master=None, matrix=None, pseudo=10.0, gap=2, gap_extend=None):
+        """The next profile of an iterated search (sw_pssm_refine): a new Pssm
+        from these hits' alignments against `pssm`, its rows the prior."""
+        idv = np.ascontiguousarray(ids, dtype=np.int32)
+        m, mp = self._master(pssm, master)
+        mat = None if matrix is None else np.ascontiguousarray(np.asarray(matrix, dtype=np.int8).reshape(625))
+        p = ctypes.c_void_p()
+        _check(lib().sw_pssm_refine(self.handle.ptr, self._d, pssm.ptr, gap, gap if gap_extend is None else gap_extend,
+                                    mp, None if mat is None else mat.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)),
+                                    float(pseudo), idv.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(idv),
+                                    ctypes.byref(p)))
+        return Pssm(self.handle, None, _adopt=p)
+
+    def search_iter(self, query_codes, rounds, inclusion_evalue=1e-3, include_max=PROFILE_MAX_HITS, pseudo=10.0,
+                    k=500, max_evalue=None, matrix=None, gap=2, gap_extend=None, final_pssm=False):
+        """The iterated search (sw_search_iter).  Returns a dict: rows (dicts
+        of id, score, evalue, bits, z in E-value order), n_pass, calib (the
+        last round's), rounds (per round run: included, added, dropped,
+        calib), converged, and pssm (the last round's Pssm) when asked for."""
+        q, qp = _u8(query_codes)
+        sc = _ScoringArg(matrix, gap, gap if gap_extend is None else gap_extend)
+        kk = max(int(k), 1)
+        ids = np.zeros(kk, dtype=np.int32)
+        scores = np.zeros(kk, dtype=np.int32)
+        sig = (Sig * kk)()
+        cal = Calib()
+        log = (IterRound * max(int(rounds), 1))()
+        nhits, npass = ctypes.c_int32(0), ctypes.c_int64(0)
+        run, conv = ctypes.c_int32(0), ctypes.c_int32(0)
+        p = ctypes.c_void_p()
+        _check(lib().sw_search_iter(self.handle.ptr, self._d, qp, len(q), sc.ptr(), rounds, float(inclusion_evalue),
+                                    include_max, float(pseudo), k, self._max_evalue(max_evalue),
+                                    ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                    scores.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), sig, ctypes.byref(nhits),
+                                    ctypes.byref(npass), ctypes.byref(cal), log, ctypes.byref(run), ctypes.byref(conv),
+                                    ctypes.byref(p) if final_pssm else None))
+        out = {"rows": [dict(id=int(ids[i]), score=int(scores[i]), **sig[i].as_dict()) for i in range(nhits.value)],
+               "n_pass": npass.value, "calib": cal, "converged": bool(conv.value),
+               "rounds": [dict(included=log[t].included, added=log[t].added, dropped=log[t].dropped,
+                               calib=log[t].calib.copy()) for t in range(run.value)]}
+        if final_pssm:
+            out["pssm"] = Pssm(self.handle, None, _adopt=p)
+        return out
+
     @staticmethod
     def _cat(queries):
         cat = np.concatenate([np.asarray(q, dtype=np.uint8) for q in queries]) if len(queries) else \
@@ -985,6 +1112,52 @@ def sig_rank_min(calib, max_evalue):
     _check(lib().sw_sig_rank_min(ctypes.byref(calib), float("inf") if max_evalue is None else float(max_evalue),
                                  ctypes.byref(r)))
     return r.value
+
+
+def profile_counts_msa(handle, msa):
+    """The integer profile tables of rows the caller supplies (uint8
+    [nrows][qlen]; sw_profile_counts_msa, the kernels' own entry point): (cnt,
+    weight, wsum) as Database.profile_counts."""
+    r = np.ascontiguousarray(msa, dtype=np.uint8)
+    if r.ndim != 2:
+        raise SWError("the rows are a [nrows][qlen] byte matrix")
+    nrows, qlen = r.shape
+    cnt = np.zeros((qlen, PROFILE_CODES), dtype=np.uint32)
+    weight = np.zeros(max(nrows, 1), dtype=np.uint64)
+    wsum = np.zeros((qlen, PROFILE_CODES), dtype=np.uint64)
+    _check(lib().sw_profile_counts_msa(handle.ptr, r.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), nrows, qlen,
+                                       cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                       weight.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                       wsum.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+    return cnt, weight[:nrows], wsum
+
+
+def matrix_lambda(matrix=None):
+    """The scale lambda of a 25 x 25 matrix under the Swiss-Prot background
+    (sw_matrix_lambda; host only; None: the reference's BLOSUM50)."""
+    m = None if matrix is None else np.ascontiguousarray(np.asarray(matrix, dtype=np.int8).reshape(625))
+    out = ctypes.c_double(0.0)
+    _check(lib().sw_matrix_lambda(None if m is None else m.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)),
+                                  ctypes.byref(out)))
+    return out.value
+
+
+def pssm_from_counts(cnt, wsum, prior_rows, matrix=None, pseudo=10.0):
+    """The [qlen][25] int8 table of integer profile tables, a prior table and
+    a matrix (sw_pssm_from_counts; host only)."""
+    c = np.ascontiguousarray(cnt, dtype=np.uint32).reshape(-1, PROFILE_CODES)
+    w = np.ascontiguousarray(wsum, dtype=np.uint64).reshape(-1, PROFILE_CODES)
+    pr = np.ascontiguousarray(prior_rows, dtype=np.int8).reshape(-1, SW_ALPHABET)
+    if not len(c) == len(w) == len(pr):
+        raise SWError("cnt, wsum and prior_rows have one row per position")
+    m = None if matrix is None else np.ascontiguousarray(np.asarray(matrix, dtype=np.int8).reshape(625))
+    out = np.zeros((len(c), SW_ALPHABET), dtype=np.int8)
+    i8p = ctypes.POINTER(ctypes.c_int8)
+    _check(lib().sw_pssm_from_counts(c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                     w.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), len(c),
+                                     pr.ctypes.data_as(i8p), None if m is None else m.ctypes.data_as(i8p),
+                                     float(pseudo), out.ctypes.data_as(i8p)))
+    return out
 
 
 class Group:

@@ -56,6 +56,17 @@
 // query in file order a line "# query <index from 0> <name> <length>" and
 // its hit-table rows (--hits) or id:score lines (--topk); the METRICS block
 // with M as the query length, so its GCUPS count every query's cells.
+// Iterated profile search: --iterations N with --query (sw_search_iter,
+// sw_amd.h): up to N rounds, each scanning the current profile, including the
+// subjects with E <= --inclusion-evalue X (default 1e-3) and rebuilding the
+// profile from their alignments.  It cannot be combined with --pssm,
+// --queries, --hits, --gpus N > 1 or --make-db; --topk K (1..4096, default
+// 500) and --max-evalue X bound the report; all checked before any file is
+// read.  Output after the query echo: per round
+//   # iteration <t> included <n> added <a> dropped <d>
+// then "# converged" or "# stopped after <N>", then per reported subject, in
+// E-value order, a tab-separated row: id score evalue bits.  --write-pssm FILE
+// writes the last round's profile in --pssm's format.
 //
 // Five steps: parse and validate the flags (sw_cli.h: pure, no file read),
 // read the inputs, search (sw_solver_search: one path for a FASTA and a .swdb
@@ -138,6 +149,21 @@ void print_calib(const sw_calib& c, size_t query_index) {
                      " database's size\n";
 }
 
+// --iterations: the rounds' trace, how the loop ended, and the report
+void print_iterations(const sw_search_result& r, long rounds) {
+    for (size_t t = 0; t < r.rounds.size(); ++t)
+        cout << "# iteration " << t + 1 << " included " << r.rounds[t].included << " added " << r.rounds[t].added
+             << " dropped " << r.rounds[t].dropped << "\n";
+    if (r.converged) cout << "# converged\n";
+    else cout << "# stopped after " << rounds << "\n";
+    for (size_t i = 0; i < r.scores[0].size(); ++i) {
+        char buf[96];
+        std::snprintf(buf, sizeof buf, "%d\t%d\t%.3g\t%.1f\n", r.scores[0][i].first, r.scores[0][i].second,
+                      r.iter_sigs[i].evalue, r.iter_sigs[i].bits);
+        cout << buf;
+    }
+}
+
 }  // namespace
 
 int main(int argc, char* argv[]) {
@@ -195,6 +221,12 @@ int main(int argc, char* argv[]) {
     else rq.query = &qbuf;
     rq.mode = o.hits.set ? sw_search_request::HITS : o.topk.set ? sw_search_request::TOPK : sw_search_request::SCORES;
     rq.k = static_cast<int>(o.hits.set ? o.hits.i : o.topk.set ? o.topk.i : 0);
+    if (o.iterations.set) {
+        rq.mode = sw_search_request::TOPK;
+        rq.k = o.iter_topk();
+        rq.iterations = static_cast<int>(o.iterations.i);
+        rq.inclusion_evalue = o.iter_inclusion();
+    }
     rq.evalue = o.evalue.set;
     rq.ranked = o.ranked();
     rq.max_evalue = o.max_evalue.set ? o.max_evalue.d : HUGE_VAL;  // no cutoff
@@ -204,6 +236,15 @@ int main(int argc, char* argv[]) {
     } catch (const std::exception& e) {
         std::cerr << e.what() << "\n";
         return 1;
+    }
+
+    if (o.iterations.set) {
+        print_iterations(r, o.iterations.i);
+        if (o.write_pssm.set && !sw_solver_write_pssm(o.write_pssm.text, r.final_pssm, r.final_consensus, &err)) {
+            std::cerr << "--write-pssm " << err << "\n";
+            return 1;
+        }
+        r.scores.clear();  // (printed above, with their significances)
     }
 
     // per query (--queries: a block each, in file order; index from 0, "-" for a header without a name)

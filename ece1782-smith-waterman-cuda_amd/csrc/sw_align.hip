@@ -52,8 +52,16 @@ __device__ __forceinline__ bool better(const Best& x, const Best& y) {
 // path and find the begin cell, then again storing step n (from the end) at
 // ops[len - 1 - n] where that lies inside the slot: a slot shorter than the
 // path holds the path's first ops_stride ops, from the begin cell.
-__device__ void align_walk(const AlignArgs& a, const Best& bb, const uint8_t* T, int W1, int hit) {
+//
+// The hit's query-anchored row (AlignArgs::msa, filled with kMsaNone by
+// align_row_clear before the sweep) is written in the first pass, where the
+// path is known cell by cell: an M at (i, j) puts subject residue s[j-1] at
+// position i-1, an I puts kMsaGap there, a D has no query position.  The row
+// has one byte per query position, so no slot can truncate it.
+__device__ void align_walk(const AlignArgs& a, const Best& bb, const uint8_t* T, int W1, int hit,
+                           const uint8_t* __restrict__ s) {
     char* ops = a.ops ? a.ops + static_cast<int64_t>(hit) * a.ops_stride : nullptr;
+    uint8_t* row = a.msa ? a.msa + static_cast<int64_t>(hit) * a.qlen : nullptr;
     int i = 0, j = 0;
     int64_t len = 0;
     for (int pass = 0; pass < (ops ? 2 : 1); ++pass) {
@@ -72,6 +80,7 @@ __device__ void align_walk(const AlignArgs& a, const Best& bb, const uint8_t* T,
                     continue;
                 }
                 op = 'M';
+                if (row && !pass) row[i - 1] = s[j - 1];
                 --i;
                 --j;
             } else if (state == 1) {
@@ -81,6 +90,7 @@ __device__ void align_walk(const AlignArgs& a, const Best& bb, const uint8_t* T,
             } else {
                 op = 'I';
                 state = (t & 8) ? 2 : 0;
+                if (row && !pass) row[i - 1] = kMsaGap;
                 --i;
             }
             if (pass && len - 1 - n < a.ops_stride) ops[len - 1 - n] = op;
@@ -96,6 +106,14 @@ __device__ void align_walk(const AlignArgs& a, const Best& bb, const uint8_t* T,
     r[3] = j + 1;  // s_begin
     r[4] = bb.j;   // s_end
     r[5] = static_cast<int32_t>(n);
+}
+
+// The hit's row of AlignArgs::msa starts as all kMsaNone (every thread, before
+// the sweep's first barrier; the walk's writes follow the last one).
+__device__ __forceinline__ void align_row_clear(const AlignArgs& a, int hit, int tid) {
+    if (!a.msa) return;
+    uint8_t* row = a.msa + static_cast<int64_t>(hit) * a.qlen;
+    for (int k = tid; k < a.qlen; k += kAlignThreads) row[k] = kMsaNone;
 }
 
 // The diagonal term's score S(query row i, subject code c), i 1-based: the two
@@ -136,6 +154,7 @@ __global__ __launch_bounds__(kAlignThreads) void sw_align_linear(AlignArgs a) {
     if constexpr (Score::kStaged)
         for (int k = tid; k < 625; k += kAlignThreads) smat[k] = a.mat[k];
     for (int k = tid; k < 3 * W1; k += kAlignThreads) Hb[k] = 0;
+    align_row_clear(a, hit, tid);
     __syncthreads();
 
     Best b = {0, 0, 0};
@@ -168,7 +187,7 @@ __global__ __launch_bounds__(kAlignThreads) void sw_align_linear(AlignArgs a) {
         if (tid < w && better(red[tid + w], red[tid])) red[tid] = red[tid + w];
         __syncthreads();
     }
-    if (tid == 0) align_walk(a, red[0], T, W1, hit);
+    if (tid == 0) align_walk(a, red[0], T, W1, hit, s);
 }
 
 // Affine gaps (Gotoh; a k-gap costs gap + (k - 1) gap_extend).  The reference
@@ -201,6 +220,7 @@ __global__ __launch_bounds__(kAlignThreads) void sw_align_affine(AlignArgs a) {
     if constexpr (Score::kStaged)
         for (int k = tid; k < 625; k += kAlignThreads) smat[k] = a.mat[k];
     for (int k = tid; k < 3 * W1; k += kAlignThreads) Hb[k] = 0;
+    align_row_clear(a, hit, tid);
     for (int k = tid; k < 4 * W1; k += kAlignThreads) Eb[k] = NEG;  // E and F
     __syncthreads();
 
@@ -243,7 +263,7 @@ __global__ __launch_bounds__(kAlignThreads) void sw_align_affine(AlignArgs a) {
         if (tid < w && better(red[tid + w], red[tid])) red[tid] = red[tid + w];
         __syncthreads();
     }
-    if (tid == 0) align_walk(a, red[0], T, W1, hit);
+    if (tid == 0) align_walk(a, red[0], T, W1, hit, s);
 }
 
 hipError_t launch_align(const AlignArgs& a, hipStream_t s) {

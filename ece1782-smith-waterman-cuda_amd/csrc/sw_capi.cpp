@@ -1032,7 +1032,7 @@ extern "C" {
 
 // 0.2: sw_pssm_*; 0.3: sw_hit_stats, sw_scan_hits; 0.4: sw_scan_batch_topk, sw_*_hits batch forms;
 // 0.5: sw_score_hist*, sw_calib_*, the _sig and _calib scan forms; 0.6: sw_sig_*, the _ranked scan forms
-int32_t sw_version(void) { return 10000 * 0 + 100 * 6 + 0; }
+int32_t sw_version(void) { return 10000 * 0 + 100 * 7 + 0; }
 
 #ifndef SW_SOURCE_ID
 #define SW_SOURCE_ID "unknown"

@@ -40,6 +40,9 @@ const Flag kFlags[] = {
     {"rank", TEXT, &Options::rank, 0, 0},
     {"max-evalue", POSITIVE, &Options::max_evalue, 0, 0},
     {"metrics-json", FLAG, &Options::metrics_json, 0, 0},
+    {"iterations", INT, &Options::iterations, 1, 1000},
+    {"inclusion-evalue", POSITIVE, &Options::inclusion_evalue, 0, 0},
+    {"write-pssm", TEXT, &Options::write_pssm, 0, 0},
 };
 
 const Flag* find_flag(const std::string& name) {
@@ -97,6 +100,8 @@ const char* first_of(const Options& o, std::initializer_list<With> list) {
 
 }  // namespace
 
+// (The text is pinned by tests/golden/cli_flag_cases.json; --iterations,
+// --inclusion-evalue and --write-pssm are described in main.cpp and README.md.)
 const char* usage_text() {
     return "Smith-Waterman MI355X Usage:\n"
            "  --help                Display this help message\n"
@@ -152,7 +157,20 @@ Verdict validate(const Options& o) {
             if (!o.evalue.set || !o.hits.set)
                 return stop("--rank evalue needs --hits K --evalue: it orders the hit table by its evalue column\n");
         }
-        if (o.max_evalue.set) {
+        if (o.iterations.set) {
+            if (!o.iterations.ok) return stop("--iterations must be an integer in 1..1000\n");
+            if (const char* with = first_of(o, {{o.pssm, "--pssm"}, {o.queries, "--queries"}, {o.hits, "--hits"},
+                                                {o.gpus, "--gpus N > 1"}, {o.make_db, "--make-db"}}))
+                return stop(std::string("--iterations cannot be combined with ") + with + "\n");
+            if (o.topk.set && (!o.topk.ok || o.topk.i > 4096))
+                return stop("--iterations reports the --topk K most significant subjects, K an integer in 1..4096\n");
+            if (o.inclusion_evalue.set && !o.inclusion_evalue.ok) return stop("--inclusion-evalue must be a number > 0\n");
+            if (o.max_evalue.set && !o.max_evalue.ok) return stop("--max-evalue must be a number > 0\n");
+        } else if (o.inclusion_evalue.set || o.write_pssm.set) {
+            return stop(std::string(o.inclusion_evalue.set ? "--inclusion-evalue" : "--write-pssm") +
+                        " needs --iterations N: it belongs to the iterated search\n");
+        }
+        if (o.max_evalue.set && !o.iterations.set) {
             if (!o.rank.set) return stop("--max-evalue needs --rank evalue: the cutoff is applied by the ranking\n");
             if (!o.max_evalue.ok) return stop("--max-evalue must be a number > 0\n");
         }

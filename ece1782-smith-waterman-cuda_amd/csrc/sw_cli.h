@@ -21,13 +21,16 @@ struct Value {
 struct Options {
     bool help = false;
     Value query, pssm, queries, db, make_db, gpus, matrix, gap_open, gap_extend, topk, hits, evalue, rank, max_evalue,
-        metrics_json;
+        metrics_json, iterations, inclusion_evalue, write_pssm;
 
     // the scoring is the reference's unless one of its flags is given
     bool custom() const { return matrix.set || gap_open.set || gap_extend.set; }
     int gap_open_cost() const { return gap_open.set ? static_cast<int>(gap_open.i) : 2; }
     int gap_extend_cost() const { return gap_extend.set ? static_cast<int>(gap_extend.i) : gap_open_cost(); }
     bool ranked() const { return rank.set; }
+    // the iterated search: its report's size and its inclusion threshold
+    int iter_topk() const { return topk.set ? static_cast<int>(topk.i) : 500; }
+    double iter_inclusion() const { return inclusion_evalue.set ? inclusion_evalue.d : 1e-3; }
     // a .swdb file (sw_db_save) in the place of a FASTA database
     bool binary_db() const {
         return db.text.size() > 5 && db.text.compare(db.text.size() - 5, 5, ".swdb") == 0;

@@ -369,4 +369,15 @@ int scan_impl(sw_handle* h, const sw_db* db, const QuerySrc& src, int32_t* score
 int hist_after(sw_handle* h, sw_db* db, const int32_t* scores_dev, uint32_t* hist_dev);
 int ensure_topk_work(sw_handle* h, size_t need);  // the handle's top-K workspace holds `need` bytes
 
+// ---- sw_search.cpp: what sw_refine.cpp builds on -------------------------------
+int ensure_scores(sw_handle* h, size_t n);                     // the handle's score buffer holds n int32
+int ensure_hist_host(sw_handle* h, size_t n, uint32_t** out);  // its pinned landing area holds n calibration tables
+void calib_of(const sw_db* db, const uint32_t* hist, int32_t qlen, sw_calib* out);
+// The traceback of ids[0 .. n); msa_dev (nullable, device [n][qlen]): the hits' query-anchored rows too.
+int align_impl(sw_handle* h, const sw_db* db, const QuerySrc& src, const int32_t* ids, int32_t n, sw_alignment* out,
+               char* ops, int64_t ops_stride, uint8_t* msa_dev);
+// The key pass, the selection and (rows_dev non-null) the gather of sw_sig_topk_device, enqueued.
+int sig_topk_enqueue(sw_handle* h, sw_db* db, const int32_t* scores_dev, const int32_t* adj_host, int32_t max_len,
+                     int64_t r_min, int32_t k, int64_t* keys_out_dev, uint32_t* count_out_dev, int32_t* rows_dev);
+
 }  // namespace swd

@@ -378,8 +378,31 @@ struct AlignArgs {
     int32_t* out;              // per hit: score, q_begin, q_end, s_begin, s_end, ops_len
     char* ops;                 // per hit: ops_stride bytes (may be null)
     int64_t ops_stride;
+    // the hit's query-anchored row (sw_msa.hip's input; may be null): qlen
+    // bytes per hit, position i the subject's code under an M, kMsaGap under an
+    // I, kMsaNone outside the path's query span; never truncated
+    uint8_t* msa = nullptr;
 };
 hipError_t launch_align(const AlignArgs& a, hipStream_t s);
+
+// Query-anchored alignment rows and their integer profile tables (sw_msa.hip;
+// include/sw_amd.h "iterated profile search").  rows is [nrows][qlen] bytes,
+// row-major; only codes 0 .. kMsaCodes - 1 are counted.
+constexpr int kMsaCodes = 20;
+constexpr uint8_t kMsaGap = 25, kMsaNone = 26;
+constexpr int kMsaTile = 64;    // columns per workgroup of the two column kernels (one per lane)
+constexpr int kMsaWaves = 4;    // ... whose waves take the rows r = wave (mod kMsaWaves)
+struct MsaArgs {
+    const uint8_t* rows;
+    int32_t nrows, qlen;
+    uint32_t* cnt;     // [qlen][20]
+    uint32_t* term;    // [qlen][20]: floor(2^30 / (k_i cnt)), 0 where cnt is 0
+    uint64_t* weight;  // [nrows]
+    uint64_t* wsum;    // [qlen][20]
+};
+// The three launches in stream order: column counts and terms, row weights,
+// column weighted sums.  nrows >= 1, qlen >= 1.
+hipError_t launch_msa_tables(const MsaArgs& a, hipStream_t s);
 
 // Hit table (sw_hits.hip, sw_hits_rules.h): one workgroup of kHitsWaves waves
 // per hit, each wave in sw_intra's shape, thread t owning kHitsRowsPerLane

@@ -13,7 +13,7 @@
 
 using namespace swd;
 
-namespace {
+namespace swd {
 
 int ensure_scores(sw_handle* h, size_t n) {
     if (n > h->scores_cap) {
@@ -24,6 +24,10 @@ int ensure_scores(sw_handle* h, size_t n) {
     }
     return SW_OK;
 }
+
+}  // namespace swd
+
+namespace {
 
 // sw_scan / sw_scan_pssm: the synchronous scan into host memory.
 int scan_host(sw_handle* h, const sw_db* db, const QuerySrc& src, int32_t* scores_host) {
@@ -108,11 +112,16 @@ int topk_impl(sw_handle* h, const int32_t* scores, const int64_t* keys, int64_t 
     return SW_OK;
 }
 
+}  // namespace
+
+namespace swd {
+
 // sw_align / sw_align_pssm: one traceback path; the forms differ in what is
 // uploaded (the codes and the matrix, or nothing: the table is resident) and
-// in the kernel's score functor (sw_align.hip).
+// in the kernel's score functor (sw_align.hip).  msa_dev (nullable, device
+// [n][qlen]): every hit's query-anchored row too (sw_refine.cpp).
 int align_impl(sw_handle* h, const sw_db* cdb, const QuerySrc& src, const int32_t* ids, int32_t n,
-               sw_alignment* out, char* ops, int64_t ops_stride) {
+               sw_alignment* out, char* ops, int64_t ops_stride, uint8_t* msa_dev) {
     sw_db* db = mutable_db(cdb);
     const uint8_t* query = src.codes;
     const int32_t qlen = src.qlen;
@@ -191,6 +200,7 @@ int align_impl(sw_handle* h, const sw_db* cdb, const QuerySrc& src, const int32_
         a.out = dout.get();
         a.ops = dops.get();
         a.ops_stride = ops ? ops_stride : 0;
+        a.msa = msa_dev ? msa_dev + static_cast<int64_t>(k0) * qlen : nullptr;
         HIPCHECK(swk::launch_align(a, s));
         HIPCHECK(hipMemcpyAsync(hout.data(), dout.get(), hout.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         if (ops)
@@ -211,6 +221,10 @@ int align_impl(sw_handle* h, const sw_db* cdb, const QuerySrc& src, const int32_
     }
     return SW_OK;
 }
+
+}  // namespace swd
+
+namespace {
 
 // The hit table (sw_hits.hip): the rows of the pairs (query qidx[k], result
 // id ids[k]), k in [0, n), into out[k]; qidx null: every pair is query 0's
@@ -329,6 +343,10 @@ int check_batch_args(sw_handle* h, const sw_db* db, const uint8_t* queries, cons
     return SW_OK;
 }
 
+}  // namespace
+
+namespace swd {
+
 // The handle's pinned landing area holds at least n tables.
 int ensure_hist_host(sw_handle* h, size_t n, uint32_t** out) {
     if (n > h->hist_cap) {
@@ -348,6 +366,10 @@ void calib_of(const sw_db* db, const uint32_t* hist, int32_t qlen, sw_calib* out
     swcalib::fit(hist, qlen, out);
     out->n_skipped = db->n - out->n_db;
 }
+
+}  // namespace swd
+
+namespace {
 
 // What the four scan-and-hits entry points check first (*nhits starts at 0).
 int check_hits_args(sw_handle* h, const sw_db* db, int32_t nq, int32_t k, sw_hit* out, int32_t* nhits, bool with_sig,
@@ -402,6 +424,10 @@ int scan_hits(sw_handle* h, const sw_db* db, const uint8_t* queries, const int64
     return check_fault(h);
 }
 
+}  // namespace
+
+namespace swd {
+
 // ---- ranking by E-value (include/sw_amd.h; sw_sigkeys.hip) ---------------------
 // sw_sig_topk_device's enqueue, on the handle's stream: the adjustment table
 // goes up, the count is zeroed, every subject's key is written into the
@@ -436,6 +462,10 @@ int sig_topk_enqueue(sw_handle* h, sw_db* db, const int32_t* scores_dev, const i
     }
     return SW_OK;
 }
+
+}  // namespace swd
+
+namespace {
 
 // What the ranked forms bring down: per query k keys, the count of subjects
 // that passed, the calibration, and (PSSM form) k gathered rows of 4 ints.
@@ -875,13 +905,13 @@ int sw_scan_pssm_topk_ranked(sw_handle* h, const sw_db* db, const sw_pssm* p, in
 // ---- traceback --------------------------------------------------------------
 int sw_align(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
              const int32_t* ids, int32_t n, sw_alignment* out, char* ops, int64_t ops_stride) {
-    return align_impl(h, db, seq_src(query, qlen, sc), ids, n, out, ops, ops_stride);
+    return align_impl(h, db, seq_src(query, qlen, sc), ids, n, out, ops, ops_stride, nullptr);
 }
 
 int sw_align_pssm(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open, int32_t gap_extend,
                   const int32_t* ids, int32_t n, sw_alignment* out, char* ops, int64_t ops_stride) {
     if (int rc = check_pssm(h, p, gap_open, gap_extend)) return rc;
-    return align_impl(h, db, pssm_src(p, gap_open, gap_extend), ids, n, out, ops, ops_stride);
+    return align_impl(h, db, pssm_src(p, gap_open, gap_extend), ids, n, out, ops, ops_stride, nullptr);
 }
 
 int sw_score_pair(sw_handle* h, const uint8_t* query, int32_t qlen, const uint8_t* subject, int32_t slen,

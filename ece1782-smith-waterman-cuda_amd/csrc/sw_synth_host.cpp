@@ -12,10 +12,6 @@ namespace swk {
 
 namespace {
 
-// Swiss-Prot composition (percent), codes 0..19 = A R N D C Q E G H I L K M F
-// P S T W Y V (the same table as synth.py).
-const double kSwissProtFreq[20] = {8.25, 5.53, 4.06, 5.45, 1.37, 3.93, 6.75, 7.07, 2.27, 5.96,
-                                   9.66, 5.84, 2.42, 3.86, 4.70, 6.56, 5.34, 1.08, 2.92, 6.87};
 constexpr uint64_t kLenSalt = 0x4C454E475448ull;  // "LENGTH"
 
 // Acklam's rational approximation of the standard normal quantile.

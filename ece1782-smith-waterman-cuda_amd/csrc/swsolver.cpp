@@ -282,7 +282,12 @@ std::string entry_name(const sw_search_request& rq, bool from_file, bool group, 
 sw_search_result search(FASTADatabase* fdb, const std::string& file, const sw_search_request& rq,
                         CharPath cp = CharPath::NO) {
     const bool batch = rq.queries != nullptr, hits = rq.mode == sw_search_request::HITS;
+    const bool iter = rq.iterations > 0;
     const int k = rq.k;
+    if (iter && (!rq.query || rq.mode != sw_search_request::TOPK || k < 1 || k > 4096 || rq.evalue || rq.ranked ||
+                 !(rq.inclusion_evalue > 0) || !(rq.max_evalue > 0)))
+        throw std::invalid_argument("an iterated search takes one query, reports its 1 <= k <= 4096 most significant "
+                                    "subjects and needs E-value bounds > 0");
     if (!rq.query + !rq.queries + !rq.pssm != 2)
         throw std::invalid_argument("a search takes one of a query, a batch of queries and a PSSM");
     if ((hits && rq.pssm) || (rq.evalue && !hits) || (rq.ranked && !rq.evalue))
@@ -296,16 +301,17 @@ sw_search_result search(FASTADatabase* fdb, const std::string& file, const sw_se
     // and of SWSolver.cu:267-269?  The padding scores 0 under the reference's
     // table alone, so a set scoring drops it; a hit table's coordinates are
     // those of the sequences as written; batches and PSSMs never had it.
-    const bool as_written = hits || batch || rq.pssm || g_sc.custom;
+    const bool as_written = hits || batch || rq.pssm || iter || g_sc.custom;
     Subjects s = fdb ? Subjects(*fdb, as_written && cp == CharPath::NO) : Subjects(file);
     const double t_solve = now_s();  // a loaded file's solve_s: the search once the subjects are in hand
     const int64_t n = s.n();
     const bool no_id = std::any_of(s.ids.begin(), s.ids.end(), [](int32_t id) { return id < 0; });
-    if (fdb && no_id && (hits || batch))
-        throw std::invalid_argument(batch ? "a batch of queries needs record ids (a FASTA header per subject)"
-                                          : "the hit table needs record ids (a FASTA header per subject)");
+    if (fdb && no_id && (hits || batch || iter))
+        throw std::invalid_argument(batch  ? "a batch of queries needs record ids (a FASTA header per subject)"
+                                    : iter ? "an iterated search needs record ids (a FASTA header per subject)"
+                                           : "the hit table needs record ids (a FASTA header per subject)");
     // every score to the host: the plain scan, and a top-K ranked there
-    const bool host_rank = rq.mode == sw_search_request::TOPK && (k > 4096 || (fdb && (no_id || n == 0)));
+    const bool host_rank = rq.mode == sw_search_request::TOPK && !iter && (k > 4096 || (fdb && (no_id || n == 0)));
     const bool all_scores = rq.mode == sw_search_request::SCORES || host_rank;
 
     std::vector<uint8_t> qc;
@@ -327,7 +333,7 @@ sw_search_result search(FASTADatabase* fdb, const std::string& file, const sw_se
     r.padded_residues = s.padded_sum;
     r.scores.resize(hits ? 0 : static_cast<size_t>(nq));
     // only a FASTA's plain scan and top-K are sharded over several GPUs
-    const bool sharded = fdb && rq.query && !hits && gpus() > 1;
+    const bool sharded = fdb && rq.query && !hits && !iter && gpus() > 1;
     g_timing.gpus = sharded ? gpus() : 1;
     if (n == 0 && all_scores && !rq.pssm) return r;
 
@@ -361,7 +367,7 @@ sw_search_result search(FASTADatabase* fdb, const std::string& file, const sw_se
     const sw_db* db = s.db.get();
     const size_t table = hits ? static_cast<size_t>(nq) * static_cast<size_t>(k) : 0;
     std::vector<int32_t> scores(static_cast<size_t>(all_scores ? (s.from_file ? s.max_id + 1 : n) : 0), 0);
-    std::vector<int64_t> keys(all_scores || hits ? 0 : static_cast<size_t>(nq) * static_cast<size_t>(k));
+    std::vector<int64_t> keys(all_scores || hits || iter ? 0 : static_cast<size_t>(nq) * static_cast<size_t>(k));
     std::vector<sw_hit> rows(table);
     std::vector<sw_sig> sigs(rq.evalue ? table : 0);
     std::vector<int32_t> nhits(hits ? static_cast<size_t>(nq) : 0, 0);  // a ranked query's row count is its own
@@ -375,6 +381,27 @@ sw_search_result search(FASTADatabase* fdb, const std::string& file, const sw_se
             else if (rq.pssm) rc = sw_scan_pssm(h, db, pssm.get(), g_sc.go, g_sc.ge, scores.data());
             else if (sharded) rc = sw_group_scan(g, s.gdb.get(), qc.data(), ql, &sc, scores.data());
             else rc = sw_scan(h, db, qc.data(), ql, &sc, scores.data());
+        } else if (iter) {
+            // the iterated search (sw_amd.h sw_search_iter): the report in E-value order, the
+            // rounds' trace and the last round's profile with the query as its consensus
+            std::vector<int32_t> ids(static_cast<size_t>(k)), sco(static_cast<size_t>(k));
+            r.iter_sigs.resize(static_cast<size_t>(k));
+            r.rounds.resize(static_cast<size_t>(rq.iterations));
+            int32_t m = 0, run = 0, conv = 0;
+            sw_pssm* last = nullptr;
+            rc = sw_search_iter(h, db, qc.data(), ql, &sc, rq.iterations, rq.inclusion_evalue, 4096, 10.0, k, rq.max_evalue,
+                                ids.data(), sco.data(), r.iter_sigs.data(), &m, &r.iter_n_pass, &r.iter_calib,
+                                r.rounds.data(), &run, &conv, &last);
+            pssm.reset(last);
+            if (rc == SW_OK) {
+                r.rounds.resize(static_cast<size_t>(run));
+                r.iter_sigs.resize(static_cast<size_t>(m));
+                r.converged = conv != 0;
+                for (int32_t i = 0; i < m; ++i) r.scores[0].push_back(std::make_pair(ids[i], sco[i]));
+                r.final_pssm.resize(static_cast<size_t>(ql) * 25);
+                rc = sw_pssm_rows(last, r.final_pssm.data());
+                r.final_consensus = *rq.query;
+            }
         } else if (!hits) {
             if (batch) rc = sw_scan_batch_topk(h, db, qc.data(), qoffs.data(), nq, &sc, k, keys.data());
             else if (rq.pssm) rc = sw_scan_pssm_topk(h, db, pssm.get(), g_sc.go, g_sc.ge, k, keys.data());
@@ -621,6 +648,42 @@ bool sw_solver_read_pssm(const std::string& path, std::vector<int8_t>* rows, std
     }
     if (!header) return bad("no header line of residue letters");
     if (nrows == 0) return bad("no rows after the header");
+    return true;
+}
+
+bool sw_solver_write_pssm(const std::string& path, const std::vector<int8_t>& rows, const std::string& consensus,
+                          std::string* err) {
+    auto bad = [&](const std::string& why) {
+        if (err) *err = path + ": " + why;
+        return false;
+    };
+    static const char kLetters[] = "ARNDCQEGHILKMFPSTWYVBJZX*";
+    const size_t n = rows.size() / 25;
+    if (rows.size() % 25 != 0 || n == 0) return bad("a PSSM is [positions][25], positions >= 1");
+    if (!consensus.empty() && consensus.size() != n) return bad("the consensus has one letter per position");
+    for (int8_t v : rows)
+        if (v < -100 || v > 100) return bad("entries must be in -100..100");
+    std::ofstream out(path.c_str());
+    if (!out) return bad("cannot open PSSM file for writing");
+    out << "# position-specific scoring matrix: position, consensus, one score per residue code\n ";
+    for (int c = 0; c < 25; ++c) out << "   " << kLetters[c];
+    out << "\n";
+    for (size_t i = 0; i < n; ++i) {
+        // the consensus as the reader maps it: a letter of the alphabet, else '*'; none given: the best column
+        int cons = 0;
+        if (!consensus.empty()) {
+            const char* p = std::strchr(kLetters, std::toupper(static_cast<unsigned char>(consensus[i])));
+            cons = p && *p ? static_cast<int>(p - kLetters) : 24;
+        } else {
+            for (int c = 1; c < 25; ++c)
+                if (rows[i * 25 + c] > rows[i * 25 + cons]) cons = c;
+        }
+        out << (i + 1) << " " << kLetters[cons];
+        for (int c = 0; c < 25; ++c) out << " " << static_cast<int>(rows[i * 25 + c]);
+        out << "\n";
+    }
+    out.flush();
+    if (!out) return bad("write failed");
     return true;
 }
 

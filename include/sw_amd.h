@@ -653,8 +653,9 @@ SW_API int sw_scan_batch_hits_ranked(sw_handle* h, const sw_db* db, const uint8_
  *                    with the gap model given as two integers (1..1000;
  *                    equal = linear).  A PSSM scan copies nothing from the
  *                    host.  A PSSM of another handle's device is SW_E_INVALID.
- * Out of scope: batches of PSSMs, the sw_group_* forms, sw_score_pair,
- * position-specific gap costs, and building a PSSM from hits.              */
+ * Out of scope: batches of PSSMs, the sw_group_* forms, sw_score_pair and
+ * position-specific gap costs.  Building a PSSM from hits: "iterated profile
+ * search" below.                                                            */
 typedef struct sw_pssm sw_pssm;
 SW_API int sw_pssm_create(sw_handle* h, const int8_t* rows, int32_t qlen, sw_pssm** out);
 SW_API int sw_pssm_free(sw_pssm* p);
@@ -677,6 +678,111 @@ SW_API int sw_scan_pssm_topk_ranked(sw_handle* h, const sw_db* db, const sw_pssm
                                     int32_t gap_extend, int32_t k, double max_evalue, int32_t* ids,
                                     int32_t* scores, sw_sig* sig, int32_t* nhits, int64_t* n_pass,
                                     sw_calib* calib);
+
+/* ---- iterated profile search: a PSSM built from a scan's hits (0.7.0) ------
+ * The step from SSEARCH to PSI-BLAST: the subjects a calibrated E-value
+ * includes are aligned against the current profile, their alignments make a
+ * query-anchored multiple alignment, and its weighted residue counts, mixed
+ * with matrix-derived pseudocounts, are the next profile.  The rows and the
+ * counts are built on the device (the subjects' residues and the direction
+ * arrays are there; only small integer tables come down); the step from
+ * tables to scores is host arithmetic in doubles.
+ *
+ * Rows.  For n hits against a PSSM of qlen positions, msa[(n+1)][qlen] bytes:
+ *   row 0 is the master sequence (the query's codes), or all SW_MSA_NONE when
+ *   none is given; row 1+k is the alignment sw_align_pssm reports for ids[k]:
+ *   position i holds the subject's residue code under an 'M', SW_MSA_GAP under
+ *   an 'I' ('D' columns have no query position), and SW_MSA_NONE outside
+ *   [q_begin, q_end].  A hit of score 0 or an empty subject is an all-NONE row.
+ *   The walk back writes the row itself: no ops slot can truncate it.
+ * Tables (integers only: host, device and tests agree bit for bit).  Only the
+ *   codes 0..19 are counted; 20..24, GAP and NONE never are.
+ *   cnt[i][a]  uint32 [qlen][20]: rows r with msa[r][i] == a;
+ *   k_i        codes a with cnt[i][a] > 0;
+ *   term(i,a)  = floor(SW_PROFILE_ONE / (k_i cnt[i][a])): Henikoff position-
+ *              based weights in fixed point, SW_PROFILE_ONE = 2^30;
+ *   weight[r]  uint64 [n+1]: floor(u_r / cov_r), u_r the sum of
+ *              term(i, msa[r][i]) over the cov_r columns where row r holds a
+ *              counted code; 0 when cov_r is 0;
+ *   wsum[i][a] uint64 [qlen][20]: the sum of weight[r] over the rows with
+ *              msa[r][i] == a (below 2^43).
+ * From tables to a PSSM (host).  p_a: the Swiss-Prot composition the synthetic
+ *   generator draws from, normalised.  lambda: the positive root of
+ *   sum_{a,b<20} p_a p_b exp(lambda s[a][b]) = 1, by bisection in doubles; it
+ *   exists iff the expected score is negative and some entry is positive
+ *   (else SW_E_UNSUPPORTED).  For a position with T_i = sum_a wsum[i][a] > 0:
+ *   f_i(a) = wsum[i][a] / T_i, alpha = k_i - 1, beta = pseudo (in (0, 1000];
+ *   10 is the usual value), g_i(a) = p_a sum_b f_i(b) exp(lambda s[b][a]) (row:
+ *   the query-side code), Q_i(a) = (alpha f_i(a) + beta g_i(a)) / (alpha + beta),
+ *   rows[i][a] = clamp(llround(ln(Q_i(a) / p_a) / lambda), -100, 100) for
+ *   a < 20; columns 20..24 are the prior table's.  T_i = 0: the whole prior
+ *   row.  One observed residue: alpha = 0 and the row is the matrix's row for
+ *   it.  Scores stay on the matrix's scale, so the gap costs keep their meaning.
+ *
+ *   sw_pssm_rows   : the [qlen][25] table a PSSM was created from.
+ *   sw_msa_pssm    : the rows into host memory (msa_host[(n+1)][qlen]); al
+ *                    (nullable, [n]): the alignments' coordinates too.
+ *   sw_profile_counts : the rows and the three tables on the device; only the
+ *                    tables come down (each may be NULL).
+ *   sw_profile_counts_msa : the tables of rows the caller uploads
+ *                    (msa_host[nrows][qlen], 1 <= nrows <= 4097, any byte
+ *                    values): the kernels' own entry point.
+ *   sw_matrix_lambda, sw_pssm_from_counts : host only, no handle; matrix NULL:
+ *                    SW_MATRIX_BLOSUM50_REF; rows_out may alias prior_rows.
+ *   sw_pssm_refine : sw_profile_counts, sw_pssm_from_counts with the PSSM's own
+ *                    rows as the prior, sw_pssm_create.
+ *   sw_search_iter : P_1 is the table derived from the query (rows[i] =
+ *                    matrix[q[i]]).  Round t: one scan of P_t and its
+ *                    calibration, then a key pass and a selection with
+ *                    max_evalue = inclusion_evalue and k = include_max
+ *                    (1..4096): the selected ids are the included set I_t.
+ *                    Stop when t = rounds (>= 1) or I_t = I_{t-1} as sets
+ *                    (*converged = 1); else P_{t+1} = refine(P_t, I_t, master =
+ *                    the query).  The report (ids, scores, sig: the first
+ *                    *nhits = min(k, *n_pass) of [k]; calib, nullable) is a
+ *                    second key pass and selection over the LAST round's scores
+ *                    with (k, max_evalue), not another scan.  rounds_log
+ *                    (nullable, [rounds]): per round run, the included, added
+ *                    and dropped counts and that round's calibration;
+ *                    *rounds_run of them are written.  final_pssm (nullable):
+ *                    the last round's profile, the caller's to free.
+ * n is 0..4096; ids may repeat; an id the database does not hold is
+ * SW_E_INVALID.  The hits run in swplan::align_groups' launch groups.  All
+ * synchronous.  sw_align and sw_align_pssm are unchanged.
+ * Out of scope: a PSSM hit table, sw_group_*, purging near-identical rows,
+ * gaps as a 21st letter, composition-based adjustment, position-specific gap
+ * costs, batches of queries.                                               */
+#define SW_MSA_GAP 25
+#define SW_MSA_NONE 26
+#define SW_PROFILE_CODES 20
+#define SW_PROFILE_ONE 1073741824   /* 2^30 */
+#define SW_PROFILE_MAX_HITS 4096
+typedef struct sw_iter_round {
+    int32_t included;    /* |I_t| */
+    int32_t added;       /* |I_t \ I_{t-1}| (I_0 is empty) */
+    int32_t dropped;     /* |I_{t-1} \ I_t| */
+    int32_t reserved;
+    sw_calib calib;      /* round t's calibration */
+} sw_iter_round;
+SW_API int sw_pssm_rows(const sw_pssm* p, int8_t* rows);
+SW_API int sw_msa_pssm(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open, int32_t gap_extend,
+                       const uint8_t* master, const int32_t* ids, int32_t n, uint8_t* msa_host, sw_alignment* al);
+SW_API int sw_profile_counts(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open, int32_t gap_extend,
+                             const uint8_t* master, const int32_t* ids, int32_t n, uint32_t* cnt, uint64_t* weight,
+                             uint64_t* wsum);
+SW_API int sw_profile_counts_msa(sw_handle* h, const uint8_t* msa_host, int32_t nrows, int32_t qlen, uint32_t* cnt,
+                                 uint64_t* weight, uint64_t* wsum);
+SW_API int sw_matrix_lambda(const int8_t* matrix, double* lambda);
+SW_API int sw_pssm_from_counts(const uint32_t* cnt, const uint64_t* wsum, int32_t qlen, const int8_t* prior_rows,
+                               const int8_t* matrix, double pseudo, int8_t* rows_out);
+SW_API int sw_pssm_refine(sw_handle* h, const sw_db* db, const sw_pssm* p, int32_t gap_open, int32_t gap_extend,
+                          const uint8_t* master, const int8_t* matrix, double pseudo, const int32_t* ids, int32_t n,
+                          sw_pssm** out);
+SW_API int sw_search_iter(sw_handle* h, const sw_db* db, const uint8_t* query, int32_t qlen, const sw_scoring* sc,
+                          int32_t rounds, double inclusion_evalue, int32_t include_max, double pseudo, int32_t k,
+                          double max_evalue, int32_t* ids, int32_t* scores, sw_sig* sig, int32_t* nhits,
+                          int64_t* n_pass, sw_calib* calib, sw_iter_round* rounds_log, int32_t* rounds_run,
+                          int32_t* converged, sw_pssm** final_pssm);
 
 /* ---- single pair ---------------------------------------------------------
  * One query against one subject on the GPU (wavefront kernel); the GPU

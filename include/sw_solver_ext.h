@@ -148,10 +148,20 @@ std::vector<std::vector<sw_hit> > smith_waterman_cuda_batch_hits_ranked(const st
  * place, under the gaps of sw_solver_set_scoring (default 2/2), subjects as
  * written; k = 0: every subject in the reference's report order, k > 0: the
  * k best (score descending, record id ascending).  One GPU.
+ * sw_solver_write_pssm writes such a file: a '#' line, a header naming all 25
+ * codes, and per position its number, its consensus letter (consensus[i]; a
+ * byte outside the alphabet is written as '*'; an empty consensus: the
+ * best-scoring column, first in code order) and 25 scores, so that reading the
+ * file back gives the same rows and the same consensus.  False and *err for a
+ * table that is not [positions >= 1][25] within -100..100, a consensus of
+ * another length, or a file that cannot be written.
  * Out of scope: batches of PSSMs, several GPUs (sw_group_*), sw_score_pair,
- * position-specific gap costs, building a PSSM from hits. */
+ * position-specific gap costs.  Building a PSSM from hits: the iterated
+ * search below. */
 bool sw_solver_read_pssm(const std::string& path, std::vector<int8_t>* rows, std::string* consensus,
                          std::string* err);
+bool sw_solver_write_pssm(const std::string& path, const std::vector<int8_t>& rows, const std::string& consensus,
+                          std::string* err);
 std::vector<seqid_score> smith_waterman_cuda_pssm(const std::vector<int8_t>& rows, FASTADatabase& db,
                                                   int k /* 0 = all, in the reference's report order */);
 
@@ -163,6 +173,14 @@ std::vector<seqid_score> smith_waterman_cuda_pssm(const std::vector<int8_t>& row
  * with sigs and calibs under `evalue`, in E-value order with n_pass under
  * `ranked` (needs evalue; max_evalue as smith_waterman_cuda_hits_ranked's).
  * A .swdb file is scanned on one GPU whatever sw_solver_set_gpus says.
+ * The iterated search (sw_amd.h sw_search_iter; `main --iterations N`):
+ * iterations > 0 with a query, TOPK and k in 1..4096 (no evalue / ranked, one
+ * GPU, record ids): up to `iterations` rounds under inclusion_evalue, every
+ * included subject (up to 4096) and a pseudocount weight of 10; scores[0]
+ * holds the min(k, iter_n_pass) most significant subjects with E <= max_evalue
+ * (> 0; +infinity: no cutoff) of the last round in E-value order, iter_sigs
+ * their significances, rounds the trace, final_pssm / final_consensus the last
+ * round's profile and the query's letters (sw_solver_write_pssm's arguments).
  * Throws what the functions above throw. */
 struct sw_search_request {
     const std::string* query;                /* the residues as written */
@@ -172,6 +190,8 @@ struct sw_search_request {
     int k;
     bool evalue, ranked;
     double max_evalue;
+    int iterations;           /* 0: a plain search */
+    double inclusion_evalue;  /* a round includes the subjects with E <= this */
 };
 struct sw_search_result {
     std::vector<std::vector<seqid_score> > scores;
@@ -179,6 +199,14 @@ struct sw_search_result {
     std::vector<std::vector<sw_sig> > sigs;
     std::vector<sw_calib> calibs;
     std::vector<int64_t> n_pass;
+    /* the iterated search */
+    std::vector<sw_iter_round> rounds;
+    bool converged = false;
+    std::vector<sw_sig> iter_sigs;
+    int64_t iter_n_pass = 0;
+    sw_calib iter_calib = {};
+    std::vector<int8_t> final_pssm;
+    std::string final_consensus;
     /* main's METRICS: the FASTA parser's counts (subjects padded to TILE_SIZE),
      * the same for a file; the wall time of parsing a FASTA (0 for a file) and
      * of the search after it (a FASTA's: flatten, upload, scan and freeing the
