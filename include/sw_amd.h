@@ -746,6 +746,19 @@ SW_API int sw_scan_pssm_topk_ranked(sw_handle* h, const sw_db* db, const sw_pssm
  *                    and dropped counts and that round's calibration;
  *                    *rounds_run of them are written.  final_pssm (nullable):
  *                    the last round's profile, the caller's to free.
+ *                    Edges: the included, reported and fed-back ids are RESULT
+ *                    ids (whatever ids the database was created with).  A
+ *                    round that includes nothing still refines (n = 0, the
+ *                    master alone: columns 0..19 of a row become the matrix's
+ *                    for the query's residue, columns 20..24 and the rows
+ *                    where the query holds a code 20..24 stay the prior's, so
+ *                    P_2 = P_1), and the next round converges on the empty
+ *                    set; so do an empty
+ *                    database (*nhits = 0) and qlen = 0 (every score 0; the
+ *                    report under no cutoff is then the k lowest ids).
+ *                    rounds = 1 never refines and needs no lambda; rounds > 1
+ *                    under a matrix without one is SW_E_UNSUPPORTED before
+ *                    any scan.
  * n is 0..4096; ids may repeat; an id the database does not hold is
  * SW_E_INVALID.  The hits run in swplan::align_groups' launch groups.  All
  * synchronous.  sw_align and sw_align_pssm are unchanged.
