@@ -129,7 +129,7 @@ static bool degenerate(const sw_calib& c) { return (c.status & SW_CALIB_DEGENERA
 void rank_table(const sw_calib& c, int32_t max_len, int32_t* adj) {
     const bool flat = degenerate(c);
     adj[0] = 0;
-    for (int32_t L = 1; L <= max_len; ++L) {
+    for (int64_t L = 1; L <= max_len; ++L) {  // (64-bit: max_len = INT32_MAX ends the loop)
         if (flat) {
             adj[L] = 0;
             continue;

@@ -267,8 +267,10 @@ LptPlan lpt_plan(const PlanDb& db, int32_t qpad, int rows, int32_t qpad_intra, i
     const int nchp = (qpad_intra + 127) / 128;
     double inter_max = 0;
     for (const auto& e : w) inter_max = std::max(inter_max, e.first);
-    auto pair_us = [&](int64_t p) { return (db.llen[static_cast<size_t>(2 * p)] + swk::kLanes - 1) * nch *
-                                           step_us; };
+    // (in double: steps x chunks leaves int from a 2^30-residue subject's second chunk on)
+    auto steps_us = [&](int64_t k) { return (static_cast<double>(db.llen[static_cast<size_t>(k)]) + swk::kLanes - 1) *
+                                            nch * step_us; };
+    auto pair_us = [&](int64_t p) { return steps_us(2 * p); };
     int64_t npipe = 0;
     if (nchp <= swk::kWavesPerWG) {
         if (db.opts->lpt_pipe >= 0) npipe = db.opts->lpt_pipe;
@@ -296,8 +298,7 @@ LptPlan lpt_plan(const PlanDb& db, int32_t qpad, int rows, int32_t qpad_intra, i
     for (int64_t g = npipe_wg; g < iwg; ++g) {
         const int64_t first = std::max<int64_t>(8 * g, 2 * npipe);  // its longest subject not pipelined
         if (first >= db.nlong || first >= 2 * pipe_tail) continue;
-        w.emplace_back((db.llen[static_cast<size_t>(first)] + swk::kLanes - 1) * nch * step_us,
-                       static_cast<int32_t>(-1 - g));
+        w.emplace_back(steps_us(first), static_cast<int32_t>(-1 - g));
     }
     // (sw_scan_lpt item -1 - (iwg + pair)), ahead of everything
     for (int64_t p = 0; p < npipe; ++p) w.emplace_back(1e30 - p, static_cast<int32_t>(-1 - (iwg + p)));

@@ -221,7 +221,26 @@ SW_API int sw_get_opts(const sw_handle* h, sw_opts* o);
  * database is sorted, packed and uploaded ONCE and stays resident in HBM.
  *   residues : encoded subject residues, concatenated
  *   offsets  : n+1 offsets into residues (offsets[0] = 0)
- *   ids      : n result ids (NULL = 0..n-1); sw_scan writes scores[id]   */
+ *   ids      : n result ids (NULL = 0..n-1); sw_scan writes scores[id]
+ * Lengths.  A subject holds 0 .. 2^30 residues (a longer one is refused with
+ * SW_E_INVALID); a query is an int32_t count of rows, which the hit table
+ * alone bounds (sw_hit_stats and its kin refuse qlen + subject length >=
+ * 2^31); every other entry point is bounded by memory only.  sw_align
+ * stores (qlen + slen + 1)(qlen + 1) direction bytes per hit, 4.3 GB for a
+ * 65,544-row query however short the subject, one launch group per hit from
+ * 2^30 bytes on, and fails with SW_E_HIP when that cannot be allocated.
+ * Pinned bit for bit against the CPU
+ * oracle (tests/test_gpu_lengths.py): subjects of 32,760, 32,768, 35,213,
+ * 65,528, 65,536, 65,544 and 70,001 residues in the lanes (a block 70,016
+ * columns wide), as long subjects and under the library's own threshold,
+ * through every scan form, both rescue chains, the hit table, sw_align, the
+ * calibration table and the file format; queries of 32,760, 32,776, 35,213
+ * and 65,544 rows through the scans, batches, sw_score_pair, a PSSM, the hit
+ * table (129 chunks) and sw_align (direction arrays past 2^30 and 2^32
+ * bytes); a 35,213 x 35,213 pair scoring 180,000.  Beyond those the planning,
+ * packing and calibration code is checked on the CPU alone, for a subject of
+ * 2^30 residues and queries of 2^24 rows (tests/native/length_check.cpp);
+ * the kernels are not.                                                   */
 SW_API int sw_db_create(sw_handle* h, const uint8_t* residues, const int64_t* offsets,
                  int64_t n, const int32_t* ids, sw_db** out);
 SW_API int sw_db_free(sw_db* db);
